@@ -9,6 +9,11 @@ shared-prefix prompts with random-init weights (no network for datasets or
 checkpoints).
 
   python bench.py --gpus N --steps K --warmup W [--mode mono|pd|fc]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given and prints the result line; anything that needs
+runs of its own belongs behind --full.
 
 A "step" is one node iteration (engine decode iteration + any scheduled
 prefill chunk + one control-plane exchange). The timed region brackets
@@ -64,7 +69,48 @@ def parse_args():
     p.add_argument("--ttft-slo-ms", type=float, default=2000.0)
     p.add_argument("--device", default=None, help="override (cpu for tests)")
     p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the model passes "
+                        "of the LAST timed step returned to the engine as "
+                        "DIR/<name>.npy (float32): <pass>_logits and "
+                        "<pass>_next_tokens for pass in decode|prefill. "
+                        "Logits larger than the size budget are stored as a "
+                        "fixed column sample seeded by --seed. Inputs are a "
+                        "pure function of the arguments, so two builds can "
+                        "be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that a plain "
+                        "run skips. There are none today: every figure on "
+                        "the result line falls out of the timed steps, so "
+                        "this is accepted and changes nothing")
     return p.parse_args()
+
+
+# --dump-outputs size budget over all ranks and arrays (float32 on disk)
+DUMP_BUDGET_BYTES = 32 << 20
+
+
+def dump_outputs(dirpath, passes, rank, world, seed):
+    """Write the (kind, logits) pairs recorded in the last timed step."""
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    if not passes:
+        print(f"WARNING: rank {rank} ran no model pass in the last timed "
+              "step; nothing to dump", file=sys.stderr)
+        return
+    max_elems = DUMP_BUDGET_BYTES // 4 // (world * len(passes))
+    for kind, logits in passes:
+        rows, vocab = logits.shape
+        tokens = logits.argmax(dim=-1)     # the engine's greedy sample
+        if rows * (vocab + 1) > max_elems:
+            cols = np.sort(np.random.default_rng(seed).choice(
+                vocab, size=max(1, max_elems // rows - 1), replace=False))
+            logits = logits.index_select(
+                1, torch.from_numpy(cols).to(logits.device))
+        np.save(os.path.join(dirpath, f"{kind}_logits{suffix}.npy"),
+                logits.float().cpu().numpy())
+        np.save(os.path.join(dirpath, f"{kind}_next_tokens{suffix}.npy"),
+                tokens.cpu().numpy().astype(np.float32))
 
 
 def pd_topology(n: int) -> str:
@@ -259,7 +305,20 @@ def main():
         seed=args.seed)
     node = NodeRunner(cfg)
 
-    n_decode = len(node.topology.ranks_with(
+    # --dump-outputs: keep a reference to what each model pass of the
+    # current step returned (no copy, no sync inside the timed region)
+    last_passes = []
+    if args.dump_outputs:
+        model_forward = node.engine.model.forward
+
+        def recording_forward(batch, *a, **kw):
+            out = model_forward(batch, *a, **kw)
+            last_passes.append(
+                ("decode" if batch.is_decode else "prefill", out))
+            return out
+        node.engine.model.forward = recording_forward
+
+    n_decode =len(node.topology.ranks_with(
         __import__("llm_d_inference_scheduler_amd.datalayer.endpoint",
                    fromlist=["Role"]).Role.DECODE))
     target_inflight = args.concurrency * max(1, n_decode)
@@ -424,6 +483,7 @@ def main():
     comp0 = stats["completed"]
     t0 = time.perf_counter()
     for _ in range(args.steps):
+        last_passes.clear()
         feed()
         node.step()
         drain()
@@ -432,6 +492,8 @@ def main():
     elapsed = time.perf_counter() - t0
     tokens = node.engine.total_generated - tok0
     tokens_slo = node.engine.total_generated_slo - tok0_slo
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_passes, rank, world, args.seed)
 
     # MAX elapsed over ranks; SUM tokens over ranks
     if world > 1:

@@ -513,6 +513,10 @@ class TestObjectivePriorityEndToEnd:
         cfg = NodeConfig(model=TINY_LLAMA, world_size=1, topology="mono",
                          device="cpu", dtype=torch.float32, kv_blocks=16)
         node = NodeRunner(cfg)
+        # no prefill batching delay: with the engine's 60 ms default the
+        # critical prefill is first tried after 60 ms of wall clock, which
+        # a fast host does not spend in the 80-step window below
+        node.engine.prefill_max_delay_ms = 0.0
         node.datastore.put_objective(InferenceObjective(
             "critical", priority=10))
         node.datastore.put_objective(InferenceObjective(

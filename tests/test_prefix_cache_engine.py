@@ -279,7 +279,11 @@ class TestPriorityPreemptsBeforeExhaustion:
         """A higher-priority arrival whose prefill cannot allocate
         preempts the lowest-priority running request immediately instead
         of waiting for full KV exhaustion (round-2 refinement)."""
-        w = make_worker(kv_blocks=16)   # 256 token slots
+        # no prefill batching delay: with the 60 ms default the arrival's
+        # prefill is first tried after 60 ms of wall clock, which a fast
+        # host does not spend in the 60-step probe window below
+        w = make_worker(kv_blocks=16,   # 256 token slots
+                        prefill_max_delay_ms=0.0)
         # low-priority request grabs most of the pool, with a generation
         # long enough that it cannot finish within the probe window
         w.add_request(EngineRequest("low", list(range(150)), max_tokens=90,
