@@ -72,6 +72,26 @@ import os as _os
 _ATTN_CHUNK = int(_os.environ.get("LLMD_ATTN_CHUNK", "256"))
 
 
+def split_geometry(n_wgs: int, max_seq_len: Optional[int],
+                   chunk: int = _ATTN_CHUNK):
+    """Flash-decoding partition geometry: (n_parts, part_tokens) when the
+    split kernel should run for a launch of n_wgs = B*KVH workgroups over
+    sequences of up to max_seq_len tokens, else None (single-pass kernel).
+
+    The plain kernel launches only B*KVH workgroups — far short of the
+    256-CU chip's >=2 WG/CU need. Long sequences are partitioned so the grid
+    fills the chip; a combine kernel merges the unnormalized partials."""
+    if max_seq_len is None or n_wgs >= 1024 or max_seq_len <= 512:
+        return None
+    target_np = min(64, max(1, 1024 // max(1, n_wgs)))
+    # partition size: ceil-divide then round up to the kernel's
+    # online-softmax chunk
+    part = max(chunk, ((max_seq_len + target_np - 1) // target_np
+                       + chunk - 1) // chunk * chunk)
+    np_ = (max_seq_len + part - 1) // part
+    return (np_, part) if np_ > 1 else None
+
+
 def paged_attention(q: torch.Tensor, k_cache: torch.Tensor,
                     v_cache: torch.Tensor, block_tables: torch.Tensor,
                     seq_lens: torch.Tensor, scale: float,
@@ -79,23 +99,11 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor,
     if _use_hip(q):
         bt = block_tables.to(torch.int32)
         sl = seq_lens.to(torch.int32)
-        # flash-decoding sequence split: the plain kernel launches only
-        # B*KVH workgroups — far short of the 256-CU chip's >=2 WG/CU need.
-        # Partition long sequences so the grid fills the chip; a combine
-        # kernel merges the unnormalized partials.
-        n_wgs = q.shape[0] * k_cache.shape[1]
-        if max_seq_len is not None and n_wgs < 1024 and max_seq_len > 512:
-            target_np = min(64, max(1, 1024 // max(1, n_wgs)))
-            # partition size: ceil-divide then round up to the kernel's
-            # 256-token online-softmax chunk
-            c = _ATTN_CHUNK
-            part = max(c, ((max_seq_len + target_np - 1) // target_np
-                           + c - 1) // c * c)
-            np_ = (max_seq_len + part - 1) // part
-            if np_ > 1:
-                return _ext.paged_attention_split(q, k_cache, v_cache, bt,
-                                                  sl, np_, part, scale,
-                                                  _ATTN_CHUNK)
+        geom = split_geometry(q.shape[0] * k_cache.shape[1], max_seq_len)
+        if geom is not None:
+            return _ext.paged_attention_split(q, k_cache, v_cache, bt, sl,
+                                              geom[0], geom[1], scale,
+                                              _ATTN_CHUNK)
         return _ext.paged_attention(q, k_cache, v_cache, bt, sl, scale,
                                     _ATTN_CHUNK)
     return ref.paged_attention(q, k_cache, v_cache, block_tables, seq_lens,
