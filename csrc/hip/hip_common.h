@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <cstdint>
+#include <type_traits>
 
 #define WAVE 64
 
@@ -128,6 +129,21 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {
 #pragma unroll
   for (int w = 0; w < NW; ++w) total += scratch[w];
   return total;
+}
+
+// Host-side launch dispatch on the GQA group size: calls
+// f(std::integral_constant<int, QPG>{}) for the supported QPG values and
+// returns false for any other, so a launcher instantiates its kernel as
+// `decltype(Q)::value` inside a generic lambda.
+template <class F>
+bool dispatch_qpg(int qpg, F&& f) {
+  switch (qpg) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+    default: return false;
+  }
 }
 
 #define HIP_CHECK_LAST()                                              \

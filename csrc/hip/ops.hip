@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "flash_prefill.h"
+
 #define CHECK_HIP(expr)                                                    \
   do {                                                                     \
     hipError_t err__ = (expr);                                             \
@@ -42,14 +44,6 @@ hipError_t lds_paged_attention_split(const void*, const void*, const void*,
                                      float*, float*, int, int, int, int, int,
                                      int, int, int, int, int, float,
                                      hipStream_t);
-hipError_t lds_flash_prefill(const void*, const void*, const void*,
-                             const int32_t*, const int32_t*, const int32_t*,
-                             void*, int, int, int, int, int, int, int, float,
-                             hipStream_t);
-hipError_t lds_flash_prefill_glds(const void*, const void*, const void*,
-                                  const int32_t*, const int32_t*,
-                                  const int32_t*, void*, int, int, int, int,
-                                  int, int, float, hipStream_t);
 }
 
 namespace {
@@ -297,7 +291,8 @@ torch::Tensor flash_prefill(torch::Tensor q, torch::Tensor k_cache,
     const char* e = getenv("LLMD_NO_GLDS");
     return e && e[0] == '1';
   }();
-  if (!no_glds && !kv_fp8_flag(k_cache) && block_tables.size(1) <= 1024) {
+  if (!no_glds && !kv_fp8_flag(k_cache) &&
+      block_tables.size(1) <= FLASH_GLDS_BT_CAP) {
     CHECK_HIP(lds_flash_prefill_glds(
         q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
         block_tables.data_ptr<int32_t>(), seq_meta.data_ptr<int32_t>(),

@@ -280,6 +280,42 @@ __global__ __launch_bounds__(256) void paged_attention_combine_kernel(
   }
 }
 
+// ---- host launch plumbing ----
+
+struct PagedArgs {
+  dim3 grid;
+  hipStream_t stream;
+  const void *q, *k_cache, *v_cache;
+  const int32_t *block_tables, *seq_lens;
+  void* out;
+  float *part_o, *part_ml;  // null unless SPLIT
+  int kvh, bs, max_blocks, part_tokens;
+  float scale;
+};
+
+template <int QPG, bool SPLIT, typename CT, int CHUNK>
+void launch_paged(const PagedArgs& a) {
+  hipLaunchKernelGGL((paged_attention_kernel<QPG, SPLIT, CT, CHUNK>), a.grid,
+                     dim3(NW * WAVE), 0, a.stream, (const short*)a.q,
+                     (const CT*)a.k_cache, (const CT*)a.v_cache,
+                     a.block_tables, a.seq_lens, (short*)a.out, a.part_o,
+                     a.part_ml, a.kvh, a.bs, a.max_blocks, a.part_tokens,
+                     a.scale);
+}
+
+// cache element type and online-softmax chunk (256 or 512, checked by the
+// callers) picked at run time
+template <int QPG, bool SPLIT>
+void launch_paged(const PagedArgs& a, int kv_fp8, int chunk) {
+  if (kv_fp8) {
+    if (chunk == 512) launch_paged<QPG, SPLIT, unsigned char, 512>(a);
+    else launch_paged<QPG, SPLIT, unsigned char, 256>(a);
+  } else {
+    if (chunk == 512) launch_paged<QPG, SPLIT, short, 512>(a);
+    else launch_paged<QPG, SPLIT, short, 256>(a);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -293,37 +329,13 @@ hipError_t lds_paged_attention(const void* q, const void* k_cache,
   if (n_seqs == 0) return hipSuccess;
   if (head_dim != D) return hipErrorInvalidValue;
   if (chunk != 256 && chunk != 512) return hipErrorInvalidValue;
-  const int qpg = n_q_heads / kvh;
-  dim3 grid(n_seqs, kvh), block(NW * WAVE);
-#define LAUNCH_CT(QPG, CT)                                                    \
-  do {                                                                        \
-    if (chunk == 512)                                                         \
-      hipLaunchKernelGGL((paged_attention_kernel<QPG, false, CT, 512>),       \
-                         grid, block, 0, stream, (const short*)q,             \
-                         (const CT*)k_cache, (const CT*)v_cache,              \
-                         block_tables, seq_lens, (short*)out, nullptr,        \
-                         nullptr, kvh, bs, max_blocks, 0, scale);             \
-    else                                                                      \
-      hipLaunchKernelGGL((paged_attention_kernel<QPG, false, CT, 256>),       \
-                         grid, block, 0, stream, (const short*)q,             \
-                         (const CT*)k_cache, (const CT*)v_cache,              \
-                         block_tables, seq_lens, (short*)out, nullptr,        \
-                         nullptr, kvh, bs, max_blocks, 0, scale);             \
-  } while (0)
-#define LAUNCH(QPG)                                                           \
-  do {                                                                        \
-    if (kv_fp8) LAUNCH_CT(QPG, unsigned char);                                \
-    else LAUNCH_CT(QPG, short);                                               \
-  } while (0)
-  switch (qpg) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef LAUNCH
-#undef LAUNCH_CT
+  const PagedArgs a{dim3(n_seqs, kvh), stream, q, k_cache, v_cache,
+                    block_tables, seq_lens, out, nullptr, nullptr,
+                    kvh, bs, max_blocks, 0, scale};
+  const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
+    launch_paged<decltype(Q)::value, false>(a, kv_fp8, chunk);
+  });
+  if (!ok) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
   return hipSuccess;
 }
@@ -337,40 +349,17 @@ hipError_t lds_paged_attention_split(
   if (n_seqs == 0) return hipSuccess;
   if (head_dim != D || n_parts > 64) return hipErrorInvalidValue;
   if (chunk != 256 && chunk != 512) return hipErrorInvalidValue;
-  const int qpg = n_q_heads / kvh;
-  dim3 grid(n_seqs, kvh, n_parts), block(NW * WAVE);
-  dim3 cgrid(n_seqs, kvh), cblock(256);
-#define LAUNCH_CT(QPG, CT)                                                    \
-  do {                                                                        \
-    if (chunk == 512)                                                         \
-      hipLaunchKernelGGL((paged_attention_kernel<QPG, true, CT, 512>), grid,  \
-                         block, 0, stream, (const short*)q,                   \
-                         (const CT*)k_cache, (const CT*)v_cache,              \
-                         block_tables, seq_lens, (short*)out, part_o,         \
-                         part_ml, kvh, bs, max_blocks, part_tokens, scale);   \
-    else                                                                      \
-      hipLaunchKernelGGL((paged_attention_kernel<QPG, true, CT, 256>), grid,  \
-                         block, 0, stream, (const short*)q,                   \
-                         (const CT*)k_cache, (const CT*)v_cache,              \
-                         block_tables, seq_lens, (short*)out, part_o,         \
-                         part_ml, kvh, bs, max_blocks, part_tokens, scale);   \
-  } while (0)
-#define LAUNCH(QPG)                                                           \
-  do {                                                                        \
-    if (kv_fp8) LAUNCH_CT(QPG, unsigned char);                                \
-    else LAUNCH_CT(QPG, short);                                               \
-    hipLaunchKernelGGL((paged_attention_combine_kernel<QPG>), cgrid, cblock,  \
-                       0, stream, part_o, part_ml, (short*)out, kvh,          \
-                       n_parts);                                              \
-  } while (0)
-  switch (qpg) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef LAUNCH
+  const PagedArgs a{dim3(n_seqs, kvh, n_parts), stream, q, k_cache, v_cache,
+                    block_tables, seq_lens, out, part_o, part_ml,
+                    kvh, bs, max_blocks, part_tokens, scale};
+  const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
+    constexpr int QPG = decltype(Q)::value;
+    launch_paged<QPG, true>(a, kv_fp8, chunk);
+    hipLaunchKernelGGL((paged_attention_combine_kernel<QPG>),
+                       dim3(n_seqs, kvh), dim3(256), 0, stream, part_o,
+                       part_ml, (short*)out, kvh, n_parts);
+  });
+  if (!ok) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
   return hipSuccess;
 }

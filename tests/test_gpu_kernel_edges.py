@@ -62,7 +62,9 @@ def test_flash_prefill_glds(ext, qpg):
 def test_flash_prefill_plain_bf16(ext, qpg):
     """A block table wider than 1024 columns (a context beyond 16K tokens
     in production) routes bf16 KV to the plain kernel. The padding columns
-    point at the poisoned block 0."""
+    point at the poisoned block 0. Plain and glds run one tile body
+    (flash_tile.h) over the same sequence of 32-token sub-tiles, so on
+    bf16 KV their outputs are equal bit for bit."""
     case = prefill_case(qpg)
     plain = run_flash(ext, case, width=1025)
     judge("flash_prefill_plain_bf16", f"qpg{qpg}", plain, case)
@@ -71,6 +73,7 @@ def test_flash_prefill_plain_bf16(ext, qpg):
     agree = float(kc.row_rel_err(plain, glds.double()).max())
     print(f"EDGE|flash_prefill plain vs glds|qpg{qpg}|{limit:.3e}|{agree:.3e}")
     assert agree <= limit
+    assert torch.equal(plain, glds)
 
 
 @pytest.mark.parametrize("qpg", [2, 4])
