@@ -23,8 +23,14 @@ using namespace flash;
 
 constexpr int KVBLK = 2 * SUBTILE;  // tokens per staged KV tile
 
-template <int QPG, typename CT>
-__global__ __launch_bounds__(NW * WAVE, 2) void flash_prefill_kernel(
+// SCALED: the cache is fp8 with per-head scales. It is a template flag, not
+// a run-time test, so that the unscaled instantiations stay the code they
+// were: with the scale loads present the compiler schedules the fp8 kernel
+// onto 186 VGPRs (2 workgroups per CU where it had 3). The scaled
+// instantiation asks for 3 in its launch bounds and gets 168, no scratch.
+template <int QPG, typename CT, bool SCALED>
+__global__ __launch_bounds__(NW * WAVE, SCALED ? 3 : 2)
+void flash_prefill_kernel(
     const short* __restrict__ q,        // [T, QH, D]
     const CT* __restrict__ k_cache,     // [NB, KVH, BS, D] bf16|fp8
     const CT* __restrict__ v_cache,     // [NB, KVH, BS, D] bf16|fp8
@@ -32,8 +38,12 @@ __global__ __launch_bounds__(NW * WAVE, 2) void flash_prefill_kernel(
     const int32_t* __restrict__ seq_meta,      // [S, 3] start, chunk, prior
     const int32_t* __restrict__ tiles,         // [n_tiles, 2] seq, vrow0
     short* __restrict__ out,                   // [T, QH, D]
+    const float* __restrict__ k_scale,  // [KVH] fp8 dequant scale | null
+    const float* __restrict__ v_scale,  // [KVH] fp8 dequant scale | null
     int kvh, int bs, int max_blocks, float scale) {
   const int kh = blockIdx.y;
+  // scaled fp8 cache: k = byte * k_scale[kh] folds into the softmax scale
+  if (SCALED && k_scale != nullptr) scale *= k_scale[kh];
   const int tid = threadIdx.x;
   const RowGeom r = row_geom<QPG>(tiles, seq_meta, kvh);
   const int32_t* bt = block_tables + (int64_t)r.seq * max_blocks;
@@ -84,6 +94,12 @@ __global__ __launch_bounds__(NW * WAVE, 2) void flash_prefill_kernel(
     }
   }
 
+  // v = byte * v_scale[kh]: applied once to the finished output row
+  if (SCALED && v_scale != nullptr) {
+    const float vs = v_scale[kh];
+#pragma unroll
+    for (int dt = 0; dt < D / 32; ++dt) acc_o[dt] *= vs;
+  }
   store_out(out, r, l_run, acc_o);
 }
 
@@ -97,21 +113,27 @@ hipError_t lds_flash_prefill(const void* q, const void* k_cache,
                              const int32_t* seq_meta, const int32_t* tiles,
                              void* out, int n_tiles, int n_q_heads, int kvh,
                              int bs, int head_dim, int max_blocks, int kv_fp8,
-                             float scale, hipStream_t stream) {
+                             float scale, const float* k_scale,
+                             const float* v_scale, hipStream_t stream) {
   if (n_tiles == 0) return hipSuccess;
   if (head_dim != D) return hipErrorInvalidValue;
+  if (!kv_fp8 && (k_scale || v_scale)) return hipErrorInvalidValue;
   dim3 grid(n_tiles, kvh), block(NW * WAVE);
   const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
-    auto launch = [&](auto ct) {  // ct: a value of the cache element type
+    // ct: a value of the cache element type; scaled: std::true_type to
+    // read the scales
+    auto launch = [&](auto ct, auto scaled) {
       typedef decltype(ct) CT;
-      hipLaunchKernelGGL((flash_prefill_kernel<decltype(Q)::value, CT>),
-                         grid, block, 0, stream, (const short*)q,
-                         (const CT*)k_cache, (const CT*)v_cache,
-                         block_tables, seq_meta, tiles, (short*)out, kvh, bs,
-                         max_blocks, scale);
+      hipLaunchKernelGGL(
+          (flash_prefill_kernel<decltype(Q)::value, CT,
+                                decltype(scaled)::value>),
+          grid, block, 0, stream, (const short*)q, (const CT*)k_cache,
+          (const CT*)v_cache, block_tables, seq_meta, tiles, (short*)out,
+          k_scale, v_scale, kvh, bs, max_blocks, scale);
     };
-    if (kv_fp8) launch((unsigned char)0);
-    else launch((short)0);
+    if (!kv_fp8) launch((short)0, std::false_type{});
+    else if (k_scale || v_scale) launch((unsigned char)0, std::true_type{});
+    else launch((unsigned char)0, std::false_type{});
   });
   if (!ok) return hipErrorInvalidValue;
   HIP_CHECK_LAST();

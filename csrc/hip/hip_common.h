@@ -89,6 +89,33 @@ __device__ __forceinline__ void store_kv8(unsigned char* p, short8 v) {
   w[1] = hi;
 }
 
+// Scaled fp8 store: the cache byte is fp8_rne(clamp(x * inv_scale, +-448))
+// and means float(byte) * scale. The clamp is explicit fp32 so the result
+// never depends on what the pack instruction does beyond the e4m3 range;
+// the compares are false for NaN, which therefore stays NaN.
+constexpr float FP8_E4M3_MAX = 448.f;
+
+__device__ __forceinline__ float scale_clamp_fp8(short x, float inv_scale) {
+  const float y = bf16_to_f32(x) * inv_scale;
+  return y > FP8_E4M3_MAX ? FP8_E4M3_MAX
+                          : (y < -FP8_E4M3_MAX ? -FP8_E4M3_MAX : y);
+}
+
+__device__ __forceinline__ void store_kv8(unsigned char* p, short8 v,
+                                          float inv_scale) {
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = scale_clamp_fp8(v[j], inv_scale);
+  uint32_t lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+  uint32_t* w = (uint32_t*)p;
+  w[0] = lo;
+  w[1] = hi;
+}
+
 // load 8 cache elements as bf16 (LDS staging in the flash-prefill kernel)
 __device__ __forceinline__ short8 load_kv8_bf16(const short* p) {
   return *(const short8*)p;

@@ -12,13 +12,17 @@ namespace {
 
 // Scatter the freshly projected K/V of each token into its pool slot.
 //  k_new/v_new: [T, KVH, D] bf16; slot_mapping: [T] int64 (block*BS + row)
-//  k_cache/v_cache: [NB, KVH, BS, D] bf16 (one layer's slice)
+//  k_cache/v_cache: [NB, KVH, BS, D] bf16|fp8 (one layer's slice)
+//  k_inv_scale/v_inv_scale: [KVH] fp32 (1 / per-head scale of this layer),
+//  fp8 cache only; null = unscaled store
 template <typename CT>
 __global__ void reshape_and_cache_kernel(const short* __restrict__ k_new,
                                          const short* __restrict__ v_new,
                                          CT* __restrict__ k_cache,
                                          CT* __restrict__ v_cache,
                                          const int64_t* __restrict__ slots,
+                                         const float* __restrict__ k_inv_scale,
+                                         const float* __restrict__ v_inv_scale,
                                          int n_tokens, int kvh, int bs, int d) {
   const int t = blockIdx.x;
   if (t >= n_tokens) return;
@@ -33,8 +37,21 @@ __global__ void reshape_and_cache_kernel(const short* __restrict__ k_new,
     const short8* src_k = (const short8*)(k_new + ((int64_t)t * kvh + h) * d);
     const short8* src_v = (const short8*)(v_new + ((int64_t)t * kvh + h) * d);
     int64_t dst_off = (((block * kvh + h) * bs) + row) * d;
-    store_kv8(k_cache + dst_off + c * 8, src_k[c]);
-    store_kv8(v_cache + dst_off + c * 8, src_v[c]);
+    if constexpr (std::is_same<CT, unsigned char>::value) {
+      if (k_inv_scale != nullptr) {
+        store_kv8(k_cache + dst_off + c * 8, src_k[c], k_inv_scale[h]);
+      } else {
+        store_kv8(k_cache + dst_off + c * 8, src_k[c]);
+      }
+      if (v_inv_scale != nullptr) {
+        store_kv8(v_cache + dst_off + c * 8, src_v[c], v_inv_scale[h]);
+      } else {
+        store_kv8(v_cache + dst_off + c * 8, src_v[c]);
+      }
+    } else {
+      store_kv8(k_cache + dst_off + c * 8, src_k[c]);
+      store_kv8(v_cache + dst_off + c * 8, src_v[c]);
+    }
   }
 }
 
@@ -113,6 +130,8 @@ hipError_t lds_reshape_and_cache(const void* k_new, const void* v_new,
                                  void* k_cache, void* v_cache,
                                  const int64_t* slots, int n_tokens, int kvh,
                                  int bs, int d, int kv_fp8,
+                                 const float* k_inv_scale,
+                                 const float* v_inv_scale,
                                  hipStream_t stream) {
   if (n_tokens == 0) return hipSuccess;
   int threads = kvh * (d / 8);
@@ -122,12 +141,13 @@ hipError_t lds_reshape_and_cache(const void* k_new, const void* v_new,
                        dim3(n_tokens), dim3(threads), 0, stream,
                        (const short*)k_new, (const short*)v_new,
                        (unsigned char*)k_cache, (unsigned char*)v_cache,
-                       slots, n_tokens, kvh, bs, d);
+                       slots, k_inv_scale, v_inv_scale, n_tokens, kvh, bs, d);
   } else {
+    if (k_inv_scale || v_inv_scale) return hipErrorInvalidValue;
     hipLaunchKernelGGL(reshape_and_cache_kernel<short>, dim3(n_tokens),
                        dim3(threads), 0, stream, (const short*)k_new,
                        (const short*)v_new, (short*)k_cache, (short*)v_cache,
-                       slots, n_tokens, kvh, bs, d);
+                       slots, nullptr, nullptr, n_tokens, kvh, bs, d);
   }
   HIP_CHECK_LAST();
   return hipSuccess;

@@ -32,18 +32,18 @@ hipError_t lds_rope(void*, void*, const float*, const int32_t*, int, int, int,
 hipError_t lds_silu_mul(const void*, void*, int64_t, int, hipStream_t);
 hipError_t lds_reshape_and_cache(const void*, const void*, void*, void*,
                                  const int64_t*, int, int, int, int, int,
-                                 hipStream_t);
+                                 const float*, const float*, hipStream_t);
 hipError_t lds_gather_blocks(const void*, void*, const int32_t*, int, int,
                              int64_t, int64_t, int, hipStream_t);
 hipError_t lds_paged_attention(const void*, const void*, const void*,
                                const int32_t*, const int32_t*, void*, int, int,
                                int, int, int, int, int, int, float,
-                               hipStream_t);
+                               const float*, const float*, hipStream_t);
 hipError_t lds_paged_attention_split(const void*, const void*, const void*,
                                      const int32_t*, const int32_t*, void*,
                                      float*, float*, int, int, int, int, int,
                                      int, int, int, int, int, float,
-                                     hipStream_t);
+                                     const float*, const float*, hipStream_t);
 }
 
 namespace {
@@ -53,6 +53,22 @@ int kv_fp8_flag(const torch::Tensor& cache) {
   TORCH_CHECK(cache.scalar_type() == at::kBFloat16,
               "KV cache must be bf16 or fp8_e4m3fn");
   return 0;
+}
+
+// Optional per-KV-head scale vector of an fp8 cache ([KVH] fp32, one
+// layer's slice): its device pointer, or null when absent.
+const float* kv_scale_ptr(const c10::optional<torch::Tensor>& s,
+                          const torch::Tensor& cache, const char* name) {
+  if (!s.has_value()) return nullptr;
+  TORCH_CHECK(cache.scalar_type() == at::kFloat8_e4m3fn, name,
+              " is only legal with an fp8_e4m3fn KV cache");
+  TORCH_CHECK(s->is_cuda() && s->device() == cache.device(), name,
+              " must be on the KV cache's device");
+  TORCH_CHECK(s->scalar_type() == at::kFloat, name, " must be float32");
+  TORCH_CHECK(s->is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(s->numel() == cache.size(1), name, " must hold ",
+              cache.size(1), " values (one per KV head), got ", s->numel());
+  return s->data_ptr<float>();
 }
 
 hipStream_t cur_stream() {
@@ -147,15 +163,20 @@ torch::Tensor silu_mul(torch::Tensor gate_up) {
 
 void reshape_and_cache(torch::Tensor k_new, torch::Tensor v_new,
                        torch::Tensor k_cache, torch::Tensor v_cache,
-                       torch::Tensor slots) {
+                       torch::Tensor slots,
+                       c10::optional<torch::Tensor> k_inv_scale,
+                       c10::optional<torch::Tensor> v_inv_scale) {
   CHECK_GPU(k_new); CHECK_GPU(v_new); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
   CHECK_GPU(slots);
+  const float* kis = kv_scale_ptr(k_inv_scale, k_cache, "k_inv_scale");
+  const float* vis = kv_scale_ptr(v_inv_scale, v_cache, "v_inv_scale");
   int T = (int)k_new.size(0), kvh = (int)k_new.size(1), d = (int)k_new.size(2);
   int bs = (int)k_cache.size(2);
   CHECK_HIP(lds_reshape_and_cache(k_new.data_ptr(), v_new.data_ptr(),
                                   k_cache.data_ptr(), v_cache.data_ptr(),
                                   slots.data_ptr<int64_t>(), T, kvh, bs, d,
-                                  kv_fp8_flag(k_cache), cur_stream()));
+                                  kv_fp8_flag(k_cache), kis, vis,
+                                  cur_stream()));
 }
 
 void move_blocks(torch::Tensor pool, torch::Tensor staging,
@@ -236,9 +257,13 @@ torch::Tensor paged_attention(torch::Tensor q, torch::Tensor k_cache,
                               torch::Tensor v_cache,
                               torch::Tensor block_tables,
                               torch::Tensor seq_lens, double scale,
-                              int64_t chunk) {
+                              int64_t chunk,
+                              c10::optional<torch::Tensor> k_scale,
+                              c10::optional<torch::Tensor> v_scale) {
   CHECK_GPU(q); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
   CHECK_GPU(block_tables); CHECK_GPU(seq_lens);
+  const float* ks = kv_scale_ptr(k_scale, k_cache, "k_scale");
+  const float* vs = kv_scale_ptr(v_scale, v_cache, "v_scale");
   int B = (int)q.size(0), qh = (int)q.size(1), d = (int)q.size(2);
   int kvh = (int)k_cache.size(1), bs = (int)k_cache.size(2);
   auto out = torch::empty_like(q);
@@ -246,7 +271,8 @@ torch::Tensor paged_attention(torch::Tensor q, torch::Tensor k_cache,
       q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
       block_tables.data_ptr<int32_t>(), seq_lens.data_ptr<int32_t>(),
       out.data_ptr(), B, qh, kvh, bs, d, (int)block_tables.size(1),
-      kv_fp8_flag(k_cache), (int)chunk, (float)scale, cur_stream()));
+      kv_fp8_flag(k_cache), (int)chunk, (float)scale, ks, vs,
+      cur_stream()));
   return out;
 }
 
@@ -255,9 +281,13 @@ torch::Tensor paged_attention_split(torch::Tensor q, torch::Tensor k_cache,
                                     torch::Tensor block_tables,
                                     torch::Tensor seq_lens, int64_t n_parts,
                                     int64_t part_tokens, double scale,
-                                    int64_t chunk) {
+                                    int64_t chunk,
+                                    c10::optional<torch::Tensor> k_scale,
+                                    c10::optional<torch::Tensor> v_scale) {
   CHECK_GPU(q); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
   CHECK_GPU(block_tables); CHECK_GPU(seq_lens);
+  const float* ks = kv_scale_ptr(k_scale, k_cache, "k_scale");
+  const float* vs = kv_scale_ptr(v_scale, v_cache, "v_scale");
   int B = (int)q.size(0), qh = (int)q.size(1), d = (int)q.size(2);
   int kvh = (int)k_cache.size(1), bs = (int)k_cache.size(2);
   int qpg = qh / kvh;
@@ -270,16 +300,21 @@ torch::Tensor paged_attention_split(torch::Tensor q, torch::Tensor k_cache,
       block_tables.data_ptr<int32_t>(), seq_lens.data_ptr<int32_t>(),
       out.data_ptr(), part_o.data_ptr<float>(), part_ml.data_ptr<float>(), B,
       qh, kvh, bs, d, (int)block_tables.size(1), (int)n_parts,
-      (int)part_tokens, kv_fp8_flag(k_cache), (int)chunk, (float)scale, cur_stream()));
+      (int)part_tokens, kv_fp8_flag(k_cache), (int)chunk, (float)scale, ks,
+      vs, cur_stream()));
   return out;
 }
 
 torch::Tensor flash_prefill(torch::Tensor q, torch::Tensor k_cache,
                             torch::Tensor v_cache, torch::Tensor block_tables,
                             torch::Tensor seq_meta, torch::Tensor tiles,
-                            double scale) {
+                            double scale,
+                            c10::optional<torch::Tensor> k_scale,
+                            c10::optional<torch::Tensor> v_scale) {
   CHECK_GPU(q); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
   CHECK_GPU(block_tables); CHECK_GPU(seq_meta); CHECK_GPU(tiles);
+  const float* ks = kv_scale_ptr(k_scale, k_cache, "k_scale");
+  const float* vs = kv_scale_ptr(v_scale, v_cache, "v_scale");
   TORCH_CHECK(q.dtype() == torch::kBFloat16, "flash_prefill expects bf16");
   int qh = (int)q.size(1), d = (int)q.size(2);
   int kvh = (int)k_cache.size(1), bs = (int)k_cache.size(2);
@@ -305,7 +340,7 @@ torch::Tensor flash_prefill(torch::Tensor q, torch::Tensor k_cache,
       block_tables.data_ptr<int32_t>(), seq_meta.data_ptr<int32_t>(),
       tiles.data_ptr<int32_t>(), out.data_ptr(), (int)tiles.size(0), qh, kvh,
       bs, d, (int)block_tables.size(1), kv_fp8_flag(k_cache), (float)scale,
-      cur_stream()));
+      ks, vs, cur_stream()));
   return out;
 }
 
@@ -320,7 +355,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("residual") = py::none());
   m.def("rope", &rope, "in-place NeoX RoPE");
   m.def("silu_mul", &silu_mul, "fused SiLU*up on packed gate_up");
-  m.def("reshape_and_cache", &reshape_and_cache, "scatter K/V into paged pool");
+  m.def("reshape_and_cache", &reshape_and_cache,
+        "scatter K/V into paged pool", py::arg("k_new"), py::arg("v_new"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"),
+        py::arg("k_inv_scale") = py::none(),
+        py::arg("v_inv_scale") = py::none());
   m.def("move_blocks", &move_blocks, "gather/scatter KV blocks for xGMI transfer");
   m.def("ipc_alloc_tensor", &ipc_alloc_tensor,
         "hipMalloc-backed tensor (IPC-shareable, outside the caching allocator)");
@@ -332,12 +371,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_attention", &paged_attention,
         "GQA decode attention over paged KV", py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
-        py::arg("seq_lens"), py::arg("scale"), py::arg("chunk") = 256);
+        py::arg("seq_lens"), py::arg("scale"), py::arg("chunk") = 256,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("paged_attention_split", &paged_attention_split,
         "flash-decoding GQA attention with sequence partitioning",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_tables"), py::arg("seq_lens"), py::arg("n_parts"),
-        py::arg("part_tokens"), py::arg("scale"), py::arg("chunk") = 256);
+        py::arg("part_tokens"), py::arg("scale"), py::arg("chunk") = 256,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("flash_prefill", &flash_prefill,
-        "fused MFMA causal varlen prefill attention over paged KV");
+        "fused MFMA causal varlen prefill attention over paged KV",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_tables"), py::arg("seq_meta"), py::arg("tiles"),
+        py::arg("scale"), py::arg("k_scale") = py::none(),
+        py::arg("v_scale") = py::none());
 }

@@ -39,6 +39,8 @@ __global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
     short* __restrict__ out,                   // [B, QH, D]
     float* __restrict__ part_o,   // [B, KVH, NP, QPG, D] (SPLIT)
     float* __restrict__ part_ml,  // [B, KVH, NP, QPG, 2] (SPLIT)
+    const float* __restrict__ k_scale,  // [KVH] fp8 dequant scale | null
+    const float* __restrict__ v_scale,  // [KVH] fp8 dequant scale | null
     int kvh, int bs, int max_blocks, int part_tokens, float scale) {
   const int b = blockIdx.x;
   const int kh = blockIdx.y;
@@ -70,11 +72,13 @@ __global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
     return;
   }
 
-  // stage scaled Q for the group into LDS
+  // stage scaled Q for the group into LDS; a scaled fp8 K cache means
+  // k = byte * k_scale[kh], which folds into the softmax scale
+  const float q_scale = k_scale != nullptr ? scale * k_scale[kh] : scale;
   for (int i = tid; i < QPG * D; i += NW * WAVE) {
     int h = i / D, d = i % D;
     q_lds[h][d] =
-        bf16_to_f32(q[((int64_t)b * n_q_heads + qh0 + h) * D + d]) * scale;
+        bf16_to_f32(q[((int64_t)b * n_q_heads + qh0 + h) * D + d]) * q_scale;
   }
   if (tid < QPG) {
     m_sh[tid] = NEG;
@@ -201,6 +205,17 @@ __global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
     __syncthreads();  // logits reused next chunk
   }
 
+  // scaled fp8 V cache: v = byte * v_scale[kh], applied once per output
+  // (the split partials carry it, so the combine kernel is unchanged)
+  if (v_scale != nullptr) {
+    const float vs = v_scale[kh];
+#pragma unroll
+    for (int h = 0; h < QPG; ++h) {
+      o_acc[h][0] *= vs;
+      o_acc[h][1] *= vs;
+    }
+  }
+
   // ---- combine partial o across waves ----
 #pragma unroll
   for (int h = 0; h < QPG; ++h) {
@@ -289,6 +304,7 @@ struct PagedArgs {
   const int32_t *block_tables, *seq_lens;
   void* out;
   float *part_o, *part_ml;  // null unless SPLIT
+  const float *k_scale, *v_scale;  // null = unscaled cache
   int kvh, bs, max_blocks, part_tokens;
   float scale;
 };
@@ -299,8 +315,8 @@ void launch_paged(const PagedArgs& a) {
                      dim3(NW * WAVE), 0, a.stream, (const short*)a.q,
                      (const CT*)a.k_cache, (const CT*)a.v_cache,
                      a.block_tables, a.seq_lens, (short*)a.out, a.part_o,
-                     a.part_ml, a.kvh, a.bs, a.max_blocks, a.part_tokens,
-                     a.scale);
+                     a.part_ml, a.k_scale, a.v_scale, a.kvh, a.bs,
+                     a.max_blocks, a.part_tokens, a.scale);
 }
 
 // cache element type and online-softmax chunk (256 or 512, checked by the
@@ -325,13 +341,15 @@ hipError_t lds_paged_attention(const void* q, const void* k_cache,
                                const int32_t* seq_lens, void* out, int n_seqs,
                                int n_q_heads, int kvh, int bs, int head_dim,
                                int max_blocks, int kv_fp8, int chunk,
-                               float scale, hipStream_t stream) {
+                               float scale, const float* k_scale,
+                               const float* v_scale, hipStream_t stream) {
   if (n_seqs == 0) return hipSuccess;
   if (head_dim != D) return hipErrorInvalidValue;
   if (chunk != 256 && chunk != 512) return hipErrorInvalidValue;
+  if (!kv_fp8 && (k_scale || v_scale)) return hipErrorInvalidValue;
   const PagedArgs a{dim3(n_seqs, kvh), stream, q, k_cache, v_cache,
                     block_tables, seq_lens, out, nullptr, nullptr,
-                    kvh, bs, max_blocks, 0, scale};
+                    k_scale, v_scale, kvh, bs, max_blocks, 0, scale};
   const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
     launch_paged<decltype(Q)::value, false>(a, kv_fp8, chunk);
   });
@@ -345,13 +363,16 @@ hipError_t lds_paged_attention_split(
     const int32_t* block_tables, const int32_t* seq_lens, void* out,
     float* part_o, float* part_ml, int n_seqs, int n_q_heads, int kvh, int bs,
     int head_dim, int max_blocks, int n_parts, int part_tokens, int kv_fp8,
-    int chunk, float scale, hipStream_t stream) {
+    int chunk, float scale, const float* k_scale, const float* v_scale,
+    hipStream_t stream) {
   if (n_seqs == 0) return hipSuccess;
   if (head_dim != D || n_parts > 64) return hipErrorInvalidValue;
   if (chunk != 256 && chunk != 512) return hipErrorInvalidValue;
+  if (!kv_fp8 && (k_scale || v_scale)) return hipErrorInvalidValue;
   const PagedArgs a{dim3(n_seqs, kvh, n_parts), stream, q, k_cache, v_cache,
                     block_tables, seq_lens, out, part_o, part_ml,
-                    kvh, bs, max_blocks, part_tokens, scale};
+                    k_scale, v_scale, kvh, bs, max_blocks, part_tokens,
+                    scale};
   const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
     constexpr int QPG = decltype(Q)::value;
     launch_paged<QPG, true>(a, kv_fp8, chunk);

@@ -36,19 +36,54 @@ def block_hashes(prompt_tokens: Sequence[int], block_size: int = BLOCK_SIZE,
                           seed)
 
 
+FP8_E4M3_MAX = 448.0
+
+
+def scales_from_amax(amax: torch.Tensor, headroom: float = 2.0
+                     ) -> torch.Tensor:
+    """Per-head fp8 scales from observed absolute maxima (any shape):
+    2 ** ceil(log2(amax * headroom / 448)), and 1.0 where amax == 0, as
+    fp32. So amax * headroom / scale <= 448 < 2 * amax * headroom / scale.
+
+    Powers of two keep dequantisation exact (the multiply only moves the
+    exponent) and make ranks that calibrate independently agree although
+    their GEMMs differ in the last bit: amax has to cross a binade edge
+    before a scale changes.
+
+    headroom=2.0 leaves one binade above the calibration maximum for
+    traffic the calibration did not see. It costs an e4m3 value no mantissa
+    bits, only one binade of underflow range out of about fifteen. That
+    default is reasoned, not measured."""
+    if headroom <= 0:
+        raise ValueError("headroom must be > 0")
+    a = torch.as_tensor(amax).detach().double().cpu()
+    if not bool((torch.isfinite(a) & (a >= 0)).all()):
+        raise ValueError("amax must be finite and >= 0")
+    # frexp: x = m * 2**e with m in [0.5, 1), so ceil(log2(x)) is e, or
+    # e - 1 for an exact power of two; no rounding of a logarithm involved
+    m, e = torch.frexp(a * (float(headroom) / FP8_E4M3_MAX))
+    e = torch.where(m == 0.5, e - 1, e)
+    scale = torch.ldexp(torch.ones_like(a), e)
+    return torch.where(a == 0, torch.ones_like(a), scale).float()
+
+
 class KVPool:
     """cache_dtype: torch.bfloat16 or torch.float8_e4m3fn (OCP fp8 — halves
     KV bytes and doubles effective decode-attention bandwidth; the gfx950
     kernels convert with the hardware v_cvt_*_fp8 ops, hip_common.h).
 
-    fp8 limitation (documented, by design): K/V are stored as UNSCALED
-    e4m3 — magnitudes >448 saturate and tiny values lose precision. This
-    matches the bf16->e4m3 direct-cast mode (vLLM's fp8 KV without
-    calibration scales); K/V activations of the supported model families
-    are well inside e4m3 range at bf16 training scale, and kv_cache_dtype
-    defaults to "auto" (=compute dtype). Outlier-heavy checkpoints should
-    keep bf16 KV; per-layer scale support would require threading a scale
-    through store (kv_cache.hip) and the attention dequant path."""
+    fp8 scales: an fp8 pool may carry per-layer, per-KV-head scales
+    `scales[L, 2(K/V), KVH]` (fp32, strictly positive). A stored byte is
+    fp8_rne(clamp(float(x) * inv_scale[h], -448, +448)) with
+    inv_scale = 1.0 / scale computed once here in fp32, and a stored byte c
+    means float(c) * scale[h]. The store kernel (kv_cache.hip) applies
+    inv_scale; the attention kernels fold k_scale into the softmax scale
+    and apply v_scale once per output row. `scales is None` is the
+    unscaled direct-cast mode (magnitudes above 448 saturate, small values
+    lose bits), which every kernel still serves on its original code path.
+    Scales change what the stored bytes mean: set them only on an empty
+    pool (EngineWorker.set_kv_scales), and ranks that exchange blocks must
+    agree on `scales_id`."""
 
     def __init__(self, config: ModelConfig, num_blocks: int,
                  device: torch.device, dtype: torch.dtype = torch.bfloat16,
@@ -56,6 +91,9 @@ class KVPool:
                  cache_dtype: torch.dtype = None,
                  ipc_alloc: bool = False):
         self.cfg = config
+        self.scales: Optional[torch.Tensor] = None       # [L, 2, KVH] fp32
+        self.inv_scales: Optional[torch.Tensor] = None   # 1.0 / scales
+        self._layer_views = None
         self.num_blocks = num_blocks
         self.block_size = block_size
         self.device = device
@@ -80,6 +118,87 @@ class KVPool:
 
     def layer(self, li: int):
         return self.tensor[li, 0], self.tensor[li, 1]
+
+    # ---- fp8 scales ------------------------------------------------------
+    def layer_scales(self, li: int):
+        """(k_scale, v_scale, k_inv_scale, v_inv_scale) views [KVH] of one
+        layer, or four Nones when the pool is unscaled."""
+        if self.scales is None:
+            return None, None, None, None
+        return self._layer_views[li]
+
+    def all_layer_scales(self):
+        """layer_scales(li) for every layer (the views are built once, not
+        per step), or None when the pool is unscaled."""
+        return None if self.scales is None else self._layer_views
+
+    def _scales_shape(self):
+        return (self.cfg.num_layers, self.cfg.num_kv_heads)
+
+    def set_scales(self, k, v) -> None:
+        """k, v: [L, KVH] (tensor or nested lists), finite and > 0. Both
+        None returns the pool to unscaled mode."""
+        if k is None and v is None:
+            self.scales = self.inv_scales = self._layer_views = None
+            return
+        if self.cache_dtype != torch.float8_e4m3fn:
+            raise ValueError("KV scales are only legal with an fp8 cache, "
+                             f"this pool is {self.cache_dtype}")
+        want = self._scales_shape()
+        parts = []
+        for name, s in (("k", k), ("v", v)):
+            t = torch.as_tensor(s, dtype=torch.float32).detach().cpu()
+            if tuple(t.shape) != want:
+                raise ValueError(
+                    f"{name} scales have shape {tuple(t.shape)}, the model "
+                    f"needs (num_layers, num_kv_heads) = {want}")
+            if not bool((torch.isfinite(t) & (t > 0)).all()):
+                raise ValueError(f"{name} scales must be finite and > 0")
+            parts.append(t)
+        scales = torch.stack(parts, dim=1).contiguous()      # [L, 2, KVH]
+        self.scales = scales.to(self.device)
+        self.inv_scales = (1.0 / scales).to(self.device)
+        self._layer_views = [
+            (self.scales[li, 0], self.scales[li, 1],
+             self.inv_scales[li, 0], self.inv_scales[li, 1])
+            for li in range(self.cfg.num_layers)]
+
+    @property
+    def scales_id(self) -> str:
+        """Short hex digest of the scale bytes; "" when unscaled. Ranks
+        compare it before adopting each other's blocks."""
+        if self.scales is None:
+            return ""
+        import hashlib
+        raw = self.scales.detach().cpu().contiguous().numpy().tobytes()
+        return hashlib.sha256(raw).hexdigest()[:16]
+
+    def save_scales(self, path: str) -> None:
+        """JSON {"k": [[L x KVH]], "v": [[L x KVH]]}. Python floats are
+        doubles and repr round-trips them, so every fp32 scale reloads bit
+        for bit."""
+        if self.scales is None:
+            raise ValueError("the pool has no scales to save")
+        import json
+        s = self.scales.detach().cpu().double()
+        with open(path, "w") as f:
+            json.dump({"k": s[:, 0].tolist(), "v": s[:, 1].tolist()}, f)
+
+    def load_scales(self, path: str) -> None:
+        import json
+        with open(path) as f:
+            doc = json.load(f)
+        got = {}
+        for name in ("k", "v"):
+            if name not in doc:
+                raise ValueError(f"{path}: missing key {name!r}")
+            got[name] = torch.tensor(doc[name], dtype=torch.float64)
+            if tuple(got[name].shape) != self._scales_shape():
+                raise ValueError(
+                    f"{path}: {name} scales have shape "
+                    f"{tuple(got[name].shape)}, the model config needs "
+                    f"(num_layers, num_kv_heads) = {self._scales_shape()}")
+        self.set_scales(got["k"].float(), got["v"].float())
 
     @property
     def block_bytes(self) -> int:
@@ -256,6 +375,25 @@ class BlockManager:
     def release_blocks(self, blocks: List[int]) -> None:
         for blk in blocks:
             self._release(blk)
+
+    @property
+    def allocated_blocks(self) -> int:
+        return self.num_blocks - len(self._free_lru)
+
+    def drop_cached(self) -> int:
+        """Forget every cached block hash (the stored bytes are about to
+        mean something else, e.g. new fp8 scales) and emit the evicted
+        events, so the router's precise index follows. Returns the count."""
+        dropped = 0
+        for blk, h in enumerate(self._hash_of):
+            if h is None:
+                continue
+            if self._by_hash.get(h) == blk:
+                del self._by_hash[h]
+                self._ev_evicted.append(h)
+                dropped += 1
+            self._hash_of[blk] = None
+        return dropped
 
     def drain_events(self):
         """(stored, evicted) content-hash batches since the last drain."""

@@ -180,7 +180,19 @@ class EngineWorker:
                  prefill_max_delay_ms: float = 60.0,
                  ipc_pool: bool = False,
                  overlap_streams: Optional[bool] = None,
-                 seed: int = 0):
+                 seed: int = 0,
+                 kv_scales: str = "none",
+                 kv_scale_headroom: float = 2.0,
+                 kv_calib_tokens: int = 2048):
+        """kv_scales selects the per-head scales of an fp8 KV cache
+        (KVPool): "none" (unscaled direct cast), "calibrate" (run
+        calibrate_kv_scales() at start-up) or the path of a scales JSON
+        (KVPool.save_scales format). Calibration runs synthetic uniform
+        random tokens, which are not representative of real traffic; how
+        far off they are has not been measured, so a deployment with a
+        calibrated checkpoint should pass its scales file. Where fp8 falls
+        back to the compute dtype (non-GPU devices) kv_scales is accepted
+        and ignored, and pool.scales stays None."""
         self.cfg = config
         self.device = torch.device(device)
         self._is_cuda_dev = lambda: self.device.type == "cuda"
@@ -207,6 +219,9 @@ class EngineWorker:
         self.mgr = BlockManager(kv_blocks, self.pool.block_size,
                                 prefix_caching=prefix_caching)
         self.model = LlamaRunner(config, self.device, dtype, seed=seed)
+        self.seed = seed
+        self.kv_scale_headroom = kv_scale_headroom
+        self.kv_calib_tokens = kv_calib_tokens
         self.waiting: List[EngineRequest] = []
         self.running: List[EngineRequest] = []
         self._by_id: Dict[str, EngineRequest] = {}
@@ -239,6 +254,93 @@ class EngineWorker:
         self.total_generated = 0
         self.total_generated_slo = 0
         self.total_prefilled = 0
+        if kv_scales not in (None, "", "none") and \
+                self.pool.cache_dtype == torch.float8_e4m3fn:
+            if kv_scales == "calibrate":
+                self.calibrate_kv_scales()
+            else:
+                self.pool.load_scales(kv_scales)
+            log.info("fp8 KV scales", source=kv_scales,
+                     scales_id=self.pool.scales_id)
+
+    # ---- fp8 KV scales -------------------------------------------------
+    def _require_empty_pool(self, what: str) -> None:
+        if self.has_work or self.mgr.tables or self.mgr.allocated_blocks:
+            raise RuntimeError(
+                f"{what} needs an idle engine with no KV block allocated: "
+                "stored bytes mean something else under new scales")
+
+    def _invalidate_cached_kv(self) -> None:
+        # freed blocks keep their content for prefix reuse; under new
+        # scales that content is stale, so forget every hash (evicted
+        # events go out with the next drain_events)
+        self.mgr.drop_cached()
+
+    def set_kv_scales(self, k, v) -> None:
+        """Install per-layer, per-KV-head fp8 scales: k, v are [L, KVH]
+        (tensor or nested lists) or scalars applied to every head. Both
+        None returns to the unscaled cache. Raises while the engine has
+        work or any block is allocated."""
+        self._require_empty_pool("set_kv_scales")
+        if k is not None or v is not None:
+            shape = (self.cfg.num_layers, self.cfg.num_kv_heads)
+            k, v = (torch.as_tensor(s, dtype=torch.float32)
+                    for s in (k, v))
+            k = k.expand(shape) if k.dim() == 0 else k
+            v = v.expand(shape) if v.dim() == 0 else v
+        self.pool.set_scales(k, v)
+        self._invalidate_cached_kv()
+
+    def calibrate_kv_scales(self, seq_len: int = 512):
+        """Derive power-of-two scales (scales_from_amax) from the per-head
+        absolute maxima of post-RoPE K and of V over a synthetic prefill,
+        and install them. Returns (k_amax, v_amax), each [L, KVH].
+
+        ceil(kv_calib_tokens / seq_len) sequences of seq_len tokens are
+        drawn uniformly over the vocabulary from torch.Generator(seed) and
+        prefilled against a temporary bf16 scratch pool, never the real
+        one: a saturated fp8 layer would corrupt the statistics of every
+        layer after it. Runs once at start-up, in plain torch apart from
+        the model's own kernels."""
+        from .kvcache import scales_from_amax
+        self._require_empty_pool("calibrate_kv_scales")
+        if self.pool.cache_dtype != torch.float8_e4m3fn:
+            raise ValueError("KV scales are only legal with an fp8 cache")
+        c = self.cfg
+        bs = self.pool.block_size
+        seq_len = max(1, min(seq_len, self.max_model_len - 1,
+                             c.max_position))
+        n_seqs = max(1, -(-self.kv_calib_tokens // seq_len))
+        blocks_per_seq = -(-seq_len // bs)
+        gen = torch.Generator(device="cpu").manual_seed(self.seed)
+        amax = torch.zeros(c.num_layers, 2, c.num_kv_heads,
+                           dtype=torch.float32, device=self.device)
+
+        def observe(li, k, v):
+            amax[li, 0] = torch.maximum(
+                amax[li, 0], k.float().abs().amax(dim=(0, 2)))
+            amax[li, 1] = torch.maximum(
+                amax[li, 1], v.float().abs().amax(dim=(0, 2)))
+
+        # one sequence per pass against a scratch pool of exactly its size
+        scratch = torch.zeros(
+            (c.num_layers, 2, blocks_per_seq, c.num_kv_heads, bs,
+             c.head_dim), dtype=self.dtype, device=self.device)
+        table = list(range(blocks_per_seq))
+        for _ in range(n_seqs):
+            ids = torch.randint(0, c.vocab_size, (seq_len,), generator=gen,
+                                dtype=torch.int64)
+            batch = self._prefill_batch(
+                ids.numpy(), np.arange(seq_len, dtype=np.int64),
+                np.arange(seq_len, dtype=np.int64), [0, seq_len],
+                [seq_len], [table], [(0, seq_len, 0)], [])
+            self.model.forward(batch, scratch, kv_observer=observe)
+        amax = amax.cpu()
+        k = scales_from_amax(amax[:, 0], self.kv_scale_headroom)
+        v = scales_from_amax(amax[:, 1], self.kv_scale_headroom)
+        self.pool.set_scales(k, v)
+        self._invalidate_cached_kv()
+        return amax[:, 0], amax[:, 1]
 
     # ------------------------------------------------------------------
     def _reject(self, req: EngineRequest, error: str) -> None:
@@ -413,6 +515,57 @@ class EngineWorker:
         req.registered_blocks = matched // self.pool.block_size
         self.mgr.set_seq_len(req.request_id, matched)
 
+    def _prefill_batch(self, input_ids, positions, slots, seq_starts,
+                       ctx_lens, tables, metas, logit_rows,
+                       embed_rows=(), embed_vals=()) -> ForwardBatch:
+        """The ForwardBatch of one prefill pass from host-side arrays:
+        flash-prefill metadata on the GPU path, per-sequence block tables
+        for the composed path otherwise."""
+        qpg = self.cfg.num_heads // self.cfg.num_kv_heads
+        flash_ok = (self._cuda and self.cfg.head_dim == 128
+                    and qpg in (1, 2, 4, 8)
+                    and self.dtype == torch.bfloat16)
+        prefill_bt = prefill_meta = prefill_tiles = None
+        bt_list = None
+        if flash_ok:
+            maxb = max(len(t) for t in tables)
+            bt_np = np.zeros((len(tables), maxb), dtype=np.int32)
+            for i, t in enumerate(tables):
+                bt_np[i, :len(t)] = t
+            prefill_bt = torch.from_numpy(bt_np).to(self.device,
+                                                    non_blocking=True)
+            prefill_meta = torch.tensor(metas, dtype=torch.int32).to(
+                self.device, non_blocking=True)
+            tl = [(i, v0) for i, (_, chunk, _) in enumerate(metas)
+                  for v0 in range(0, chunk * qpg, 128)]
+            prefill_tiles = torch.tensor(tl, dtype=torch.int32).to(
+                self.device, non_blocking=True)
+        else:
+            bt_list = [torch.tensor(t, dtype=torch.int32,
+                                    device=self.device) for t in tables]
+        batch = ForwardBatch(
+            input_ids=torch.from_numpy(input_ids).to(self.device,
+                                                     non_blocking=True),
+            positions=torch.from_numpy(
+                positions.astype(np.int32)).to(self.device,
+                                               non_blocking=True),
+            slot_mapping=torch.from_numpy(slots).to(self.device,
+                                                    non_blocking=True),
+            is_decode=False, seq_starts=seq_starts, ctx_lens=ctx_lens,
+            prefill_block_tables=bt_list,
+            prefill_bt=prefill_bt, prefill_meta=prefill_meta,
+            prefill_tiles=prefill_tiles,
+            logit_rows=torch.tensor(logit_rows, dtype=torch.int64,
+                                    device=self.device)
+            if logit_rows else torch.zeros(0, dtype=torch.int64,
+                                           device=self.device),
+            embed_rows=torch.tensor(list(embed_rows), dtype=torch.int64,
+                                    device=self.device)
+            if embed_rows else None,
+            embed_values=torch.cat(list(embed_vals)).to(self.device)
+            if embed_vals else None)
+        return batch
+
     def _prefill_pass(self) -> List[RequestOutput]:
         budget = self.prefill_chunk_tokens
         selected: List[tuple] = []
@@ -488,52 +641,13 @@ class EngineWorker:
         positions = np.concatenate(pos_np)
         slots = np.concatenate(slots_np)
 
-        qpg = self.cfg.num_heads // self.cfg.num_kv_heads
-        flash_ok = (self._cuda and self.cfg.head_dim == 128
-                    and qpg in (1, 2, 4, 8)
-                    and self.dtype == torch.bfloat16)
-        prefill_bt = prefill_meta = prefill_tiles = None
-        bt_list = None
-        if flash_ok:
-            maxb = max(len(t) for t in tables)
-            bt_np = np.zeros((len(tables), maxb), dtype=np.int32)
-            for i, t in enumerate(tables):
-                bt_np[i, :len(t)] = t
-            prefill_bt = torch.from_numpy(bt_np).to(self.device,
-                                                    non_blocking=True)
-            prefill_meta = torch.tensor(metas, dtype=torch.int32).to(
-                self.device, non_blocking=True)
-            tl = [(i, v0) for i, (_, chunk, _) in enumerate(metas)
-                  for v0 in range(0, chunk * qpg, 128)]
-            prefill_tiles = torch.tensor(tl, dtype=torch.int32).to(
-                self.device, non_blocking=True)
-        else:
-            bt_list = [torch.tensor(t, dtype=torch.int32,
-                                    device=self.device) for t in tables]
-        batch = ForwardBatch(
-            input_ids=torch.from_numpy(input_ids).to(self.device,
-                                                     non_blocking=True),
-            positions=torch.from_numpy(
-                positions.astype(np.int32)).to(self.device,
-                                               non_blocking=True),
-            slot_mapping=torch.from_numpy(slots).to(self.device,
-                                                    non_blocking=True),
-            is_decode=False, seq_starts=seq_starts, ctx_lens=ctx_lens,
-            prefill_block_tables=bt_list,
-            prefill_bt=prefill_bt, prefill_meta=prefill_meta,
-            prefill_tiles=prefill_tiles,
-            logit_rows=torch.tensor(logit_rows, dtype=torch.int64,
-                                    device=self.device)
-            if logit_rows else torch.zeros(0, dtype=torch.int64,
-                                           device=self.device),
-            embed_rows=torch.tensor(embed_rows, dtype=torch.int64,
-                                    device=self.device)
-            if embed_rows else None,
-            embed_values=torch.cat(embed_vals).to(self.device)
-            if embed_vals else None)
+        batch = self._prefill_batch(input_ids, positions, slots, seq_starts,
+                                    ctx_lens, tables, metas, logit_rows,
+                                    embed_rows, embed_vals)
         embedding_reqs = [r for r in finishing if r.is_embedding]
         hidden_or_logits = self.model.forward(
-            batch, self.pool.tensor, embeddings_out=bool(embedding_reqs))
+            batch, self.pool.tensor, embeddings_out=bool(embedding_reqs),
+            kv_scales=self.pool.all_layer_scales())
 
         outputs: List[RequestOutput] = []
         now = time.time()
@@ -671,7 +785,8 @@ class EngineWorker:
             block_tables=bt_rows, seq_lens=new_len,
             max_seq_len=max(self.mgr.seq_lens[r.request_id]
                             for r in active))
-        logits = self.model.forward(batch, self.pool.tensor)
+        logits = self.model.forward(batch, self.pool.tensor,
+                                    kv_scales=self.pool.all_layer_scales())
         any_temp = any(r.temperature > 0 for r in active)
         tok = self._sample_device(logits, rows_t, any_temp)
         st.last_tok.index_copy_(0, rows_t, tok)

@@ -141,9 +141,16 @@ class LlamaRunner:
 
     # ------------------------------------------------------------------
     def forward(self, batch: ForwardBatch, kv_pool: torch.Tensor,
-                embeddings_out: bool = False) -> torch.Tensor:
+                embeddings_out: bool = False,
+                kv_scales=None, kv_observer=None) -> torch.Tensor:
         """Returns logits [n_logit_rows, vocab] (or final hidden states for
-        embeddings_out). kv_pool: [L, 2, NB, KVH, BS, D]."""
+        embeddings_out). kv_pool: [L, 2, NB, KVH, BS, D].
+
+        kv_scales: the pool's scales for a scaled fp8 cache
+        (KVPool.all_layer_scales(): per layer the [KVH] fp32 views k_scale,
+        v_scale, k_inv_scale, v_inv_scale), None otherwise.
+        kv_observer(li, k, v), if given, sees each layer's post-RoPE K and
+        its V [T, KVH, D] just before the store (calibration)."""
         c = self.cfg
         hidden = self.embed[batch.input_ids]
         if batch.embed_rows is not None and batch.embed_rows.numel():
@@ -177,14 +184,22 @@ class LlamaRunner:
             ops.rope(q, k, self.cos_sin, pos32)
             k_cache = kv_pool[li, 0]
             v_cache = kv_pool[li, 1]
-            ops.reshape_and_cache(k, v, k_cache, v_cache, batch.slot_mapping)
+            if kv_observer is not None:
+                kv_observer(li, k, v)
+            k_scale = v_scale = k_inv = v_inv = None
+            if kv_scales is not None:
+                k_scale, v_scale, k_inv, v_inv = kv_scales[li]
+            ops.reshape_and_cache(k, v, k_cache, v_cache, batch.slot_mapping,
+                                  k_inv_scale=k_inv, v_inv_scale=v_inv)
             if batch.is_decode:
                 attn = ops.paged_attention(q, k_cache, v_cache,
                                            batch.block_tables, batch.seq_lens,
                                            self.scale,
-                                           max_seq_len=batch.max_seq_len)
+                                           max_seq_len=batch.max_seq_len,
+                                           k_scale=k_scale, v_scale=v_scale)
             else:
-                attn = self._prefill_attention(batch, q, k_cache, v_cache)
+                attn = self._prefill_attention(batch, q, k_cache, v_cache,
+                                               k_scale, v_scale)
             o = attn.view(T, c.q_size) @ layer["wo"]
             normed2 = ops.rmsnorm(o, layer["post_norm"], c.rms_eps,
                                   residual=residual)
@@ -202,7 +217,10 @@ class LlamaRunner:
 
     def _prefill_attention(self, batch: ForwardBatch, q: torch.Tensor,
                            k_cache: torch.Tensor,
-                           v_cache: torch.Tensor) -> torch.Tensor:
+                           v_cache: torch.Tensor,
+                           k_scale: Optional[torch.Tensor] = None,
+                           v_scale: Optional[torch.Tensor] = None
+                           ) -> torch.Tensor:
         """Causal varlen attention per sequence. GPU: fused MFMA flash
         kernel (flash_prefill.hip) — S never materialized. CPU fallback:
         composed chunked torch attention over pool-gathered KV."""
@@ -212,7 +230,8 @@ class LlamaRunner:
                 and c.num_heads // c.num_kv_heads in (1, 2, 4, 8)):
             return ops.flash_prefill(
                 q, k_cache, v_cache, batch.prefill_bt, batch.prefill_meta,
-                batch.prefill_tiles, self.scale)
+                batch.prefill_tiles, self.scale,
+                k_scale=k_scale, v_scale=v_scale)
         qpg = c.num_heads // c.num_kv_heads
         out = torch.empty_like(q)
         starts = batch.seq_starts
@@ -224,8 +243,8 @@ class LlamaRunner:
             kk, vv = ops_ref.gather_prefix(k_cache, v_cache,
                                            batch.prefill_block_tables[i], ctx)
             # [KVH, ctx, D]
-            kk = kk.permute(1, 0, 2)
-            vv = vv.permute(1, 0, 2)
+            kk = ops_ref.dequant(kk.permute(1, 0, 2), k_scale)
+            vv = ops_ref.dequant(vv.permute(1, 0, 2), v_scale)
             qi = q[s:e].view(chunk, c.num_kv_heads, qpg,
                              c.head_dim).permute(1, 2, 0, 3)  # [KVH,qpg,chunk,D]
             scores = torch.einsum("hgtd,hsd->hgts", qi.float(), kk.float())

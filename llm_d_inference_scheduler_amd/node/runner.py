@@ -11,6 +11,7 @@ Plays two reference roles at once:
 All ranks run `step()` in lockstep; one control-plane mailbox exchange per
 step carries assignments, metrics, KV-ready notices and completions.
 """
+import os
 import queue as queue_mod
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -83,6 +84,14 @@ class NodeConfig:
     kv_blocks: Optional[int] = None
     kv_budget_bytes: int = 8 << 30
     kv_cache_dtype: str = "auto"    # auto|bf16|fp8 (fp8 = OCP e4m3 cache)
+    # per-head scales of an fp8 cache (engine/worker.py): "none",
+    # "calibrate" or the path of a scales JSON. Defaults from the
+    # environment variable LLMD_KV_SCALES so a benchmark run can select
+    # scales without a flag of its own.
+    kv_scales: str = field(
+        default_factory=lambda: os.environ.get("LLMD_KV_SCALES") or "none")
+    kv_scale_headroom: float = 2.0
+    kv_calib_tokens: int = 2048
     prefill_chunk_tokens: int = 8192
     max_decode_batch: int = 256
     flow_control: bool = False
@@ -177,7 +186,12 @@ class NodeRunner:
             ttft_slo_ms=cfg.ttft_slo_ms,
             kv_cache_dtype=cfg.kv_cache_dtype, ipc_pool=want_ipc,
             overlap_streams=cfg.overlap_streams,
-            seed=cfg.seed)
+            seed=cfg.seed, kv_scales=cfg.kv_scales,
+            kv_scale_headroom=cfg.kv_scale_headroom,
+            kv_calib_tokens=cfg.kv_calib_tokens)
+        log.info("KV cache", dtype=str(self.engine.pool.cache_dtype),
+                 kv_scales=cfg.kv_scales,
+                 scales_id=self.engine.pool.scales_id or "unscaled")
         # encode role: vision tower + URL-deduped embedding cache
         self.encoder = None
         if (self.my_spec.role & Role.ENCODE) and cfg.model.vision_hidden:
@@ -915,6 +929,9 @@ class NodeRunner:
             return
         if self.rank != dst:
             return
+        # block transfer moves raw bytes: blocks written under other fp8
+        # scales would decode to garbage here, so refuse them
+        mismatch = job.get("kv_scales_id", "") != self.engine.pool.scales_id
         pending0 = self._pending_adoption.get(req_id)
         reserved = (pending0 or {}).get("reserved")
         if pending0 is not None:
@@ -922,15 +939,23 @@ class NodeRunner:
             # arriving mid-transfer must not release blocks the in-flight
             # copy is writing (the _adopt completion owns their release)
             pending0["reserved"] = None
-        if reserved is not None and len(reserved) != n:
+        if reserved is not None and (len(reserved) != n or mismatch):
             self.engine.mgr.release_blocks(reserved)
             reserved = None
-        local = reserved if reserved is not None else \
-            self.engine.mgr.take_blocks(n)
+        if mismatch:
+            local = None
+            log.warning("kv hand-off dropped: fp8 KV scales differ",
+                        req=req_id, src_scales=job.get("kv_scales_id", ""),
+                        dst_scales=self.engine.pool.scales_id)
+        else:
+            local = reserved if reserved is not None else \
+                self.engine.mgr.take_blocks(n)
         if local is None:
-            # cannot adopt (kv_exhausted): drop the hand-off
+            # cannot adopt (kv_exhausted, or foreign scales): drop the
+            # hand-off
             self._outbox.append({"type": "done", "req_id": req_id,
-                                 "error": "kv_exhausted"})
+                                 "error": "kv_scale_mismatch" if mismatch
+                                 else "kv_exhausted"})
             self._pending_adoption.pop(req_id, None)
             if peer:
                 # nothing was pulled; free the src blocks immediately
@@ -1000,7 +1025,8 @@ class NodeRunner:
                     "src": self.rank, "dst": decode_rank,
                     "blocks": out.kv_blocks, "seq_len": out.seq_len,
                     "first_token": out.first_token,
-                    "ttft_ms": out.ttft_ms})
+                    "ttft_ms": out.ttft_ms,
+                    "kv_scales_id": self.engine.pool.scales_id})
             elif out.kind == "embedding" and out.finished:
                 self._emit_done(out, tokens=[])
             else:

@@ -57,12 +57,18 @@ def silu_mul(gate_up: torch.Tensor) -> torch.Tensor:
 
 def reshape_and_cache(k_new: torch.Tensor, v_new: torch.Tensor,
                       k_cache: torch.Tensor, v_cache: torch.Tensor,
-                      slots: torch.Tensor) -> None:
+                      slots: torch.Tensor, *,
+                      k_inv_scale: Optional[torch.Tensor] = None,
+                      v_inv_scale: Optional[torch.Tensor] = None) -> None:
+    """k_inv_scale / v_inv_scale: [KVH] fp32 reciprocal per-head scales of
+    a scaled fp8 cache (engine/kvcache.py KVPool); None = unscaled."""
     if _use_hip(k_new):
         _ext.reshape_and_cache(k_new, v_new, k_cache, v_cache,
-                               slots.to(torch.int64))
+                               slots.to(torch.int64), k_inv_scale,
+                               v_inv_scale)
         return
-    ref.reshape_and_cache(k_new, v_new, k_cache, v_cache, slots)
+    ref.reshape_and_cache(k_new, v_new, k_cache, v_cache, slots,
+                          k_inv_scale=k_inv_scale, v_inv_scale=v_inv_scale)
 
 
 import os as _os
@@ -95,7 +101,11 @@ def split_geometry(n_wgs: int, max_seq_len: Optional[int],
 def paged_attention(q: torch.Tensor, k_cache: torch.Tensor,
                     v_cache: torch.Tensor, block_tables: torch.Tensor,
                     seq_lens: torch.Tensor, scale: float,
-                    max_seq_len: Optional[int] = None) -> torch.Tensor:
+                    max_seq_len: Optional[int] = None, *,
+                    k_scale: Optional[torch.Tensor] = None,
+                    v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """k_scale / v_scale: [KVH] fp32 per-head dequant scales of a scaled
+    fp8 cache; None = the cache holds the values themselves."""
     if _use_hip(q):
         bt = block_tables.to(torch.int32)
         sl = seq_lens.to(torch.int32)
@@ -103,21 +113,24 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor,
         if geom is not None:
             return _ext.paged_attention_split(q, k_cache, v_cache, bt, sl,
                                               geom[0], geom[1], scale,
-                                              _ATTN_CHUNK)
+                                              _ATTN_CHUNK, k_scale, v_scale)
         return _ext.paged_attention(q, k_cache, v_cache, bt, sl, scale,
-                                    _ATTN_CHUNK)
+                                    _ATTN_CHUNK, k_scale, v_scale)
     return ref.paged_attention(q, k_cache, v_cache, block_tables, seq_lens,
-                               scale)
+                               scale, k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor,
                   v_cache: torch.Tensor, block_tables: torch.Tensor,
                   seq_meta: torch.Tensor, tiles: torch.Tensor,
-                  scale: float) -> torch.Tensor:
+                  scale: float, *,
+                  k_scale: Optional[torch.Tensor] = None,
+                  v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused MFMA causal varlen prefill attention (GPU-only; callers fall
-    back to the composed reference path when unsupported)."""
+    back to the composed reference path when unsupported). k_scale /
+    v_scale as in paged_attention."""
     return hip_ops().flash_prefill(q, k_cache, v_cache, block_tables,
-                                   seq_meta, tiles, scale)
+                                   seq_meta, tiles, scale, k_scale, v_scale)
 
 
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,

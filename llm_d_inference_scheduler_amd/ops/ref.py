@@ -7,6 +7,8 @@ input dtype, mirroring the kernels' internal precision.
 """
 import torch
 
+FP8_E4M3_MAX = 448.0
+
 
 def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float,
             residual: torch.Tensor = None):
@@ -54,22 +56,44 @@ def silu_mul(gate_up: torch.Tensor) -> torch.Tensor:
 
 def reshape_and_cache(k_new: torch.Tensor, v_new: torch.Tensor,
                       k_cache: torch.Tensor, v_cache: torch.Tensor,
-                      slots: torch.Tensor) -> None:
-    """k_new/v_new: [T, KVH, D]; caches: [NB, KVH, BS, D]; slots: [T]."""
+                      slots: torch.Tensor, k_inv_scale: torch.Tensor = None,
+                      v_inv_scale: torch.Tensor = None) -> None:
+    """k_new/v_new: [T, KVH, D]; caches: [NB, KVH, BS, D]; slots: [T].
+    With an inverse scale [KVH] (scaled fp8 cache) the stored element is
+    clamp(float(x) * inv_scale[h], -448, 448) cast to the cache dtype."""
     bs = k_cache.shape[2]
+
+    def quant(x, inv):
+        if inv is None:
+            return x
+        return (x.float() * inv.float().view(-1, 1)).clamp(
+            -FP8_E4M3_MAX, FP8_E4M3_MAX).to(k_cache.dtype)
+
     for t in range(k_new.shape[0]):
         s = int(slots[t])
         if s < 0:
             continue
         blk, row = s // bs, s % bs
-        k_cache[blk, :, row, :] = k_new[t]
-        v_cache[blk, :, row, :] = v_new[t]
+        k_cache[blk, :, row, :] = quant(k_new[t], k_inv_scale)
+        v_cache[blk, :, row, :] = quant(v_new[t], v_inv_scale)
+
+
+def dequant(cache: torch.Tensor, scale: torch.Tensor = None) -> torch.Tensor:
+    """fp32 values of cache elements [..., KVH, n, D] (KVH third from the
+    end) under an optional per-head scale [KVH]: cache.float() * scale."""
+    cf = cache.float()
+    if scale is None:
+        return cf
+    return cf * scale.float().view(-1, 1, 1)
 
 
 def paged_attention(q: torch.Tensor, k_cache: torch.Tensor,
                     v_cache: torch.Tensor, block_tables: torch.Tensor,
-                    seq_lens: torch.Tensor, scale: float) -> torch.Tensor:
-    """Decode GQA attention. q: [B, QH, D] -> out [B, QH, D]."""
+                    seq_lens: torch.Tensor, scale: float,
+                    k_scale: torch.Tensor = None,
+                    v_scale: torch.Tensor = None) -> torch.Tensor:
+    """Decode GQA attention. q: [B, QH, D] -> out [B, QH, D]. k_scale /
+    v_scale [KVH]: a cache element c of head h means float(c) * scale[h]."""
     B, QH, D = q.shape
     KVH, BS = k_cache.shape[1], k_cache.shape[2]
     qpg = QH // KVH
@@ -80,8 +104,10 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor,
         blocks = block_tables[b, :nb].long()
         k = k_cache[blocks]                # [nb, KVH, BS, D]
         v = v_cache[blocks]
-        k = k.permute(1, 0, 2, 3).reshape(KVH, nb * BS, D)[:, :S].float()
-        v = v.permute(1, 0, 2, 3).reshape(KVH, nb * BS, D)[:, :S].float()
+        k = dequant(k.permute(1, 0, 2, 3).reshape(KVH, nb * BS, D)[:, :S],
+                    k_scale)
+        v = dequant(v.permute(1, 0, 2, 3).reshape(KVH, nb * BS, D)[:, :S],
+                    v_scale)
         qb = q[b].float().view(KVH, qpg, D)
         scores = torch.einsum("hgd,hsd->hgs", qb, k) * scale
         p = torch.softmax(scores, dim=-1)

@@ -36,6 +36,11 @@ def parse_args(argv=None):
     p.add_argument("--kv-gb", type=float, default=160.0)
     p.add_argument("--kv-dtype", default="auto",
                    choices=["auto", "bf16", "fp8"])
+    p.add_argument("--kv-scales", default=None,
+                   help='per-head scales of an fp8 KV cache: "none", '
+                        '"calibrate" (synthetic tokens at start-up) or the '
+                        'path of a scales JSON; default: $LLMD_KV_SCALES, '
+                        'else "none"')
     p.add_argument("--flow-control", action="store_true",
                    help="enable the flowControl feature gate")
     p.add_argument("--decode-chunk-tokens", type=int, default=0)
@@ -65,6 +70,8 @@ def build_node(args):
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("nccl" if use_gpu else "gloo")
+    scale_kw = {} if args.kv_scales is None else \
+        {"kv_scales": args.kv_scales}
     cfg = NodeConfig(
         model=model, rank=rank, world_size=world, topology=args.topology,
         epp_yaml=epp_yaml, device=device,
@@ -74,7 +81,7 @@ def build_node(args):
         kv_cache_dtype=args.kv_dtype,
         flow_control=args.flow_control,
         decode_chunk_tokens=args.decode_chunk_tokens or None,
-        seed=args.seed)
+        seed=args.seed, **scale_kw)
     return NodeRunner(cfg)
 
 

@@ -76,7 +76,9 @@ int main(int argc, char** argv) {
   hipMemcpy(dtiles, htiles.data(), htiles.size() * 4, hipMemcpyHostToDevice);
   hipError_t e = lds_flash_prefill(dq, dk, dv, dbt, dmeta, dtiles, dout,
                                    (int)htiles.size() / 2, qh, kvh, BS, Dh,
-                                   nb, /*kv_fp8=*/0, 1.f / sqrtf(128.f), 0);
+                                   nb, /*kv_fp8=*/0, 1.f / sqrtf(128.f),
+                                   /*k_scale=*/nullptr, /*v_scale=*/nullptr,
+                                   0);
   hipDeviceSynchronize();
   printf("launch: %s\n", hipGetErrorString(e));
   hipMemcpy(hout.data(), dout, hout.size() * 2, hipMemcpyDeviceToHost);
