@@ -44,6 +44,9 @@ hipError_t lds_paged_attention_split(const void*, const void*, const void*,
                                      float*, float*, int, int, int, int, int,
                                      int, int, int, int, int, float,
                                      const float*, const float*, hipStream_t);
+hipError_t lds_sample(const void*, const float*, const int32_t*, const float*,
+                      const int64_t*, const int32_t*, int, int, int, int64_t*,
+                      float*, int32_t*, float*, hipStream_t);
 }
 
 namespace {
@@ -344,6 +347,52 @@ torch::Tensor flash_prefill(torch::Tensor q, torch::Tensor k_cache,
   return out;
 }
 
+// ---- sampler ----
+
+// One per-row parameter vector of sample(): [B], on the logits' device.
+void check_sample_param(const torch::Tensor& t, const torch::Tensor& logits,
+                        at::ScalarType dtype, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == logits.device(), name,
+              " must be on the logits' device");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", dtype);
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == logits.size(0), name,
+              " must hold ", logits.size(0), " values (one per row), got ",
+              t.numel());
+}
+
+std::vector<torch::Tensor> sample(torch::Tensor logits,
+                                  torch::Tensor temperature,
+                                  torch::Tensor top_k, torch::Tensor top_p,
+                                  torch::Tensor seed, torch::Tensor pos) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be on GPU");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [B, V]");
+  TORCH_CHECK(logits.is_contiguous(), "logits must be contiguous");
+  const bool f32 = logits.scalar_type() == at::kFloat;
+  TORCH_CHECK(f32 || logits.scalar_type() == at::kBFloat16,
+              "logits must be bf16 or float32");
+  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) < (1LL << 31),
+              "vocabulary size out of range");
+  check_sample_param(temperature, logits, at::kFloat, "temperature");
+  check_sample_param(top_k, logits, at::kInt, "top_k");
+  check_sample_param(top_p, logits, at::kFloat, "top_p");
+  check_sample_param(seed, logits, at::kLong, "seed");
+  check_sample_param(pos, logits, at::kInt, "pos");
+  int B = (int)logits.size(0), V = (int)logits.size(1);
+  auto opt = logits.options();
+  auto tokens = torch::empty({B}, opt.dtype(torch::kInt64));
+  auto logprobs = torch::empty({B}, opt.dtype(torch::kFloat32));
+  auto n_kept = torch::empty({B}, opt.dtype(torch::kInt32));
+  auto threshold = torch::empty({B}, opt.dtype(torch::kFloat32));
+  CHECK_HIP(lds_sample(logits.data_ptr(), temperature.data_ptr<float>(),
+                       top_k.data_ptr<int32_t>(), top_p.data_ptr<float>(),
+                       seed.data_ptr<int64_t>(), pos.data_ptr<int32_t>(), B, V,
+                       f32 ? 1 : 0, tokens.data_ptr<int64_t>(),
+                       logprobs.data_ptr<float>(), n_kept.data_ptr<int32_t>(),
+                       threshold.data_ptr<float>(), cur_stream()));
+  return {tokens, logprobs, n_kept, threshold};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -385,4 +434,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_tables"), py::arg("seq_meta"), py::arg("tiles"),
         py::arg("scale"), py::arg("k_scale") = py::none(),
         py::arg("v_scale") = py::none());
+  m.def("sample", &sample,
+        "fused temperature/top-k/top-p/seeded sampler with logprobs -> "
+        "(tokens, logprobs, n_kept, threshold)",
+        py::arg("logits"), py::arg("temperature"), py::arg("top_k"),
+        py::arg("top_p"), py::arg("seed"), py::arg("pos"));
 }

@@ -21,6 +21,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from .. import ops
 from ..datalayer.endpoint import Metrics, Role
 from ..models.configs import ModelConfig
 from ..models.llama import ForwardBatch, LlamaRunner
@@ -44,6 +45,12 @@ class EngineRequest:
     # multimodal: embeddings for the first len(prefix_embeds) prompt rows
     # (prompt_tokens must carry placeholder ids for those positions)
     prefix_embeds: "Optional[torch.Tensor]" = None
+    # fused-sampler fields (DEVELOPMENT.md "Sampling"); any of them set
+    # routes the steps this request takes part in through ops.sample
+    top_k: int = 0                  # 0 = off
+    top_p: float = 1.0              # 1.0 = off
+    seed: Optional[int] = None      # None = derived from the worker's seed
+    logprobs: bool = False          # return the sampled tokens' logprobs
     # runtime state
     computed: int = 0               # prompt tokens already prefilled
     generated: List[int] = field(default_factory=list)
@@ -54,6 +61,8 @@ class EngineRequest:
     block_hashes: Optional[object] = None   # np.uint64 per full prompt block
     registered_blocks: int = 0              # hashes published so far
     _prompt_np: Optional[object] = field(default=None, repr=False)
+    logprob_vals: List[float] = field(default_factory=list)
+    _seed64: Optional[int] = field(default=None, repr=False)  # resolved u64
 
     def __post_init__(self):
         if not self.arrival_t:
@@ -67,6 +76,13 @@ class EngineRequest:
     def token_count(self) -> int:
         """Generated + in-flight tokens (host-known without a sync)."""
         return len(self.generated) + self.inflight
+
+    @property
+    def uses_sampler(self) -> bool:
+        """True when the request sets a field only the fused sampler
+        implements."""
+        return (self.top_k > 0 or self.top_p < 1.0 or self.seed is not None
+                or self.logprobs)
 
 
 @dataclass
@@ -83,6 +99,10 @@ class RequestOutput:
     # embedding payload:
     embedding: Optional[torch.Tensor] = None
     all_tokens: Optional[List[int]] = None  # full generation, on finish
+    # logprobs=True requests: one value per entry of new_tokens, and the
+    # whole generation's on finish
+    new_logprobs: Optional[List[float]] = None
+    all_logprobs: Optional[List[float]] = None
     # usage on finish:
     prompt_tokens: int = 0
     completion_tokens: int = 0
@@ -91,6 +111,23 @@ class RequestOutput:
     tpot_ms: Optional[float] = None
     e2e_ms: Optional[float] = None
     error: str = ""                 # terminal engine-side failure
+
+
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _splitmix64(x: int) -> int:
+    """One splitmix64 output for state x (u64 in, u64 out)."""
+    z = (x + 0x9E3779B97F4A7C15) & _U64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+    return z ^ (z >> 31)
+
+
+def _as_i64(u: int) -> int:
+    """The int64 holding the bits of u64 u (sampler seeds travel as i64)."""
+    u &= _U64
+    return u - (1 << 64) if u >> 63 else u
 
 
 class DecodeState:
@@ -104,6 +141,14 @@ class DecodeState:
         self.seq_lens = None
         self.last_tok = None
         self.temps = None
+        # fused-sampler parameters per row, written in join. pos_off is the
+        # row's completion index minus its sequence length: seq_lens already
+        # advances on device every step, so the index of the token being
+        # sampled is seq_lens + pos_off with no further per-step state.
+        self.top_k = None
+        self.top_p = None
+        self.seed = None
+        self.pos_off = None
         self.free_rows: List[int] = []
         self.row_of: Dict[str, int] = {}
         self._active_ids: List[str] = []
@@ -117,12 +162,21 @@ class DecodeState:
         sl = torch.zeros(new_cap, dtype=torch.int32, device=self.device)
         lt = torch.zeros(new_cap, dtype=torch.int64, device=self.device)
         tp = torch.zeros(new_cap, dtype=torch.float32, device=self.device)
+        tk = torch.zeros(new_cap, dtype=torch.int32, device=self.device)
+        pp = torch.ones(new_cap, dtype=torch.float32, device=self.device)
+        sd = torch.zeros(new_cap, dtype=torch.int64, device=self.device)
+        po = torch.zeros(new_cap, dtype=torch.int32, device=self.device)
         if old:
             bt[:old] = self.bt
             sl[:old] = self.seq_lens
             lt[:old] = self.last_tok
             tp[:old] = self.temps
+            tk[:old] = self.top_k
+            pp[:old] = self.top_p
+            sd[:old] = self.seed
+            po[:old] = self.pos_off
         self.bt, self.seq_lens, self.last_tok, self.temps = bt, sl, lt, tp
+        self.top_k, self.top_p, self.seed, self.pos_off = tk, pp, sd, po
         self.free_rows.extend(range(new_cap - 1, old - 1, -1))
         self.capacity = new_cap
 
@@ -147,6 +201,15 @@ class DecodeState:
         self.seq_lens[row] = seq_len
         self.last_tok[row] = last_token
         self.temps[row] = req.temperature
+        if req.temperature > 0 or req.uses_sampler:
+            # (a plain greedy row never reads these: the sampler's T <= 0
+            # branch ignores filters, seed and position)
+            self.top_k[row] = req.top_k
+            self.top_p[row] = req.top_p
+            self.seed[row] = _as_i64(req._seed64 or 0)
+            # the next token sampled for this row has completion index
+            # req.token_count, at sequence length seq_len
+            self.pos_off[row] = req.token_count - seq_len
 
     def leave(self, request_id: str) -> None:
         row = self.row_of.pop(request_id, None)
@@ -220,6 +283,7 @@ class EngineWorker:
                                 prefix_caching=prefix_caching)
         self.model = LlamaRunner(config, self.device, dtype, seed=seed)
         self.seed = seed
+        self._admitted = 0      # admission counter (derived sampler seeds)
         self.kv_scale_headroom = kv_scale_headroom
         self.kv_calib_tokens = kv_calib_tokens
         self.waiting: List[EngineRequest] = []
@@ -248,6 +312,8 @@ class EngineWorker:
         self._prefill_stream = None   # lazy; see step() overlap
         self._pin = None
         self._pending = None   # (reqs, event|None, n) — one-step readback lag
+        self._pin_lp = None
+        self._pending_lp = None   # logprobs of the pending step, if sampled
         self.steps = 0
         self._rejects: List[RequestOutput] = []
         self._carry: List[RequestOutput] = []   # outputs surfaced early
@@ -389,14 +455,30 @@ class EngineWorker:
                         req=req.request_id, requested=req.max_tokens,
                         clamped=clamped)
             req.max_tokens = clamped
+        self._resolve_seed(req)
         self.waiting.append(req)
         self._by_id[req.request_id] = req
 
+    def _resolve_seed(self, req: EngineRequest) -> None:
+        """The u64 Philox key of a request: its own seed, else one derived
+        from the worker's seed and the admission counter, so a worker fed
+        the same requests in the same order repeats its draws."""
+        if req._seed64 is None:
+            if req.seed is not None:
+                req._seed64 = int(req.seed) & _U64
+            else:
+                req._seed64 = _splitmix64(
+                    _splitmix64(self.seed & _U64) ^ self._admitted)
+        self._admitted += 1
+
     def admit_transferred(self, req: EngineRequest, local_blocks: List[int],
-                          seq_len: int, first_token: int) -> None:
+                          seq_len: int, first_token: int,
+                          first_logprob: Optional[float] = None) -> None:
         """Adopt a prefilled sequence whose KV arrived over xGMI. The
         adopted full blocks are registered in the prefix cache: a
-        transferred prefix is as reusable as a locally-computed one."""
+        transferred prefix is as reusable as a locally-computed one.
+        first_logprob is the first token's logprob from the prefill side,
+        for a logprobs=True request."""
         self.mgr.adopt(req.request_id, local_blocks, seq_len)
         if req.block_hashes is None:
             req.block_hashes = block_hashes(req.prompt_tokens,
@@ -405,8 +487,10 @@ class EngineWorker:
         for b in range(full):
             self.mgr.register_block(req.request_id, b,
                                     int(req.block_hashes[b]))
+        self._resolve_seed(req)
         req.computed = req.prompt_len
         req.generated = [first_token]
+        req.logprob_vals = [] if first_logprob is None else [first_logprob]
         if not req.first_token_t:
             req.first_token_t = time.time()
         if self.ttft_slo_ms is not None and req.arrival_t and \
@@ -680,9 +764,18 @@ class EngineWorker:
         return outputs
 
     def _finish_prefills(self, finishing, logits, outputs) -> None:
-        tokens = self._sample_host(logits, [r.temperature for r in finishing])
+        lps = None
+        if any(r.uses_sampler for r in finishing):
+            tokens, lps = self._sample_first(logits, finishing)
+        else:
+            tokens = self._sample_host(logits,
+                                       [r.temperature for r in finishing])
         now = time.time()
-        for req, tok in zip(finishing, tokens):
+        for i, (req, tok) in enumerate(zip(finishing, tokens)):
+            new_lp = None
+            if req.logprobs and lps is not None:
+                new_lp = [lps[i]]
+                req.logprob_vals.append(lps[i])
             if not req.first_token_t:     # preempted reqs keep their TTFT
                 req.first_token_t = now
                 if self.ttft_slo_ms is not None and req.arrival_t and \
@@ -697,7 +790,8 @@ class EngineWorker:
                     seq_len=self.mgr.seq_lens[req.request_id],
                     first_token=int(tok), prompt_tokens=req.prompt_len,
                     cached_tokens=req.cached_tokens,
-                    ttft_ms=(now - req.arrival_t) * 1e3))
+                    ttft_ms=(now - req.arrival_t) * 1e3,
+                    new_logprobs=new_lp))
                 # blocks stay allocated until the transfer engine releases
                 self._by_id.pop(req.request_id, None)
             else:
@@ -710,7 +804,7 @@ class EngineWorker:
                 outputs.append(RequestOutput(
                     request_id=req.request_id, new_tokens=[int(tok)],
                     ttft_ms=(now - req.arrival_t) * 1e3,
-                    cached_tokens=req.cached_tokens))
+                    cached_tokens=req.cached_tokens, new_logprobs=new_lp))
                 self.total_generated += 1
 
     def release_prefilled(self, request_id: str) -> None:
@@ -787,8 +881,19 @@ class EngineWorker:
                             for r in active))
         logits = self.model.forward(batch, self.pool.tensor,
                                     kv_scales=self.pool.all_layer_scales())
-        any_temp = any(r.temperature > 0 for r in active)
-        tok = self._sample_device(logits, rows_t, any_temp)
+        lp = None
+        if any(r.uses_sampler for r in active):
+            # the fused sampler takes the whole step: T <= 0 rows go
+            # through its greedy branch; `lens` is the pre-step length
+            tok, lp, _, _ = ops.sample(
+                logits, st.temps.index_select(0, rows_t),
+                st.top_k.index_select(0, rows_t),
+                st.top_p.index_select(0, rows_t),
+                st.seed.index_select(0, rows_t),
+                lens + st.pos_off.index_select(0, rows_t))
+        else:
+            any_temp = any(r.temperature > 0 for r in active)
+            tok = self._sample_device(logits, rows_t, any_temp)
         st.last_tok.index_copy_(0, rows_t, tok)
 
         n = tok.shape[0]
@@ -798,30 +903,46 @@ class EngineWorker:
                 self._pin = torch.empty(st.capacity, dtype=torch.int64,
                                         pin_memory=True)
             self._pin[:n].copy_(tok, non_blocking=True)
+            if lp is not None:
+                # logprobs ride the same pinned read-back and event
+                if self._pin_lp is None or \
+                        self._pin_lp.shape[0] < st.capacity:
+                    self._pin_lp = torch.empty(
+                        st.capacity, dtype=torch.float32, pin_memory=True)
+                self._pin_lp[:n].copy_(lp, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             self._pending = (active, ev, n)
         else:
             self._pending = (active, None, tok)
+        self._pending_lp = lp
         return prev + finals
 
     def _collect_pending(self) -> List[RequestOutput]:
         if self._pending is None:
             return []
         reqs, ev, payload = self._pending
+        lp_t, self._pending_lp = self._pending_lp, None
         self._pending = None
+        lps = None
         if ev is not None:
             ev.synchronize()
             vals = self._pin[:payload].tolist()
+            if lp_t is not None:
+                lps = self._pin_lp[:payload].tolist()
         else:
             vals = payload.tolist()
+            if lp_t is not None:
+                lps = lp_t.tolist()
         outputs: List[RequestOutput] = []
         now = time.time()
-        for req, tok in zip(reqs, vals):
+        for i, (req, tok) in enumerate(zip(reqs, vals)):
             if self._by_id.get(req.request_id) is not req:
                 continue                      # aborted while in flight
             req.inflight -= 1
             req.generated.append(int(tok))
+            if req.logprobs and lps is not None:
+                req.logprob_vals.append(lps[i])
             self.total_generated += 1
             if req.slo_ok:
                 self.total_generated_slo += 1
@@ -832,9 +953,13 @@ class EngineWorker:
                                 new_tokens=[int(tok)], finished=finished,
                                 finish_reason="stop" if stopped
                                 else "length")
+            if req.logprobs and lps is not None:
+                out.new_logprobs = [lps[i]]
             if finished:
                 n_gen = len(req.generated)
                 out.all_tokens = list(req.generated)
+                if req.logprobs:
+                    out.all_logprobs = list(req.logprob_vals)
                 out.prompt_tokens = req.prompt_len
                 out.completion_tokens = n_gen
                 out.cached_tokens = req.cached_tokens
@@ -910,6 +1035,8 @@ class EngineWorker:
             completion_tokens=n_gen, cached_tokens=req.cached_tokens,
             ttft_ms=(req.first_token_t - req.arrival_t) * 1e3,
             e2e_ms=(now - req.arrival_t) * 1e3)
+        if req.logprobs:
+            out.all_logprobs = list(req.logprob_vals)
         if n_gen > 1:
             out.tpot_ms = (now - req.first_token_t) * 1e3 / (n_gen - 1)
         self.running.remove(req)
@@ -934,6 +1061,27 @@ class EngineWorker:
         gumbel = -torch.log(-torch.log(u).clamp_min(1e-20))
         y = y + gumbel * hot.unsqueeze(1)
         return y.argmax(dim=-1)
+
+    def _sample_first(self, logits: torch.Tensor,
+                      reqs: List[EngineRequest]):
+        """First-token sampling through the fused sampler, on the logits
+        where they live: (tokens, logprobs) as host lists. The token's
+        completion index is len(req.generated): 0, or where a preempted
+        request left off."""
+        dev = logits.device
+        tok, lp, _, _ = ops.sample(
+            logits,
+            torch.tensor([r.temperature for r in reqs],
+                         dtype=torch.float32, device=dev),
+            torch.tensor([r.top_k for r in reqs], dtype=torch.int32,
+                         device=dev),
+            torch.tensor([r.top_p for r in reqs], dtype=torch.float32,
+                         device=dev),
+            torch.tensor([_as_i64(r._seed64) for r in reqs],
+                         dtype=torch.int64, device=dev),
+            torch.tensor([len(r.generated) for r in reqs],
+                         dtype=torch.int32, device=dev))
+        return tok.tolist(), lp.tolist()
 
     def _sample_host(self, logits: torch.Tensor,
                      temps: List[float]) -> List[int]:

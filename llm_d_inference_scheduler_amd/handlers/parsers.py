@@ -72,6 +72,30 @@ def _headers_into(req: LLMRequest, headers: Dict[str, str]) -> None:
         req.target_model = forced
 
 
+def _is_int(v: Any) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _sampling_into(req: LLMRequest, top_p: Any, top_k: Any, seed: Any,
+                   p_name: str, k_name: str) -> Optional[str]:
+    """Validate and store the sampler fields (absent = None = off).
+    Returns an error message for an out-of-range value."""
+    if top_p is not None:
+        if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) \
+                or not 0.0 < float(top_p) <= 1.0:
+            return f"{p_name} must be a number in (0, 1]"
+        req.top_p = float(top_p)
+    if top_k is not None:
+        if not _is_int(top_k) or top_k < -1:
+            return f"{k_name} must be an integer >= -1"
+        req.top_k = max(0, top_k)       # -1 and 0 both mean off
+    if seed is not None:
+        if not _is_int(seed) or not 0 <= seed < 1 << 64:
+            return "seed must be a non-negative integer below 2^64"
+        req.seed = seed
+    return None
+
+
 def _extract_mm_items(messages: List[Dict[str, Any]]) -> List[MultiModalItem]:
     items: List[MultiModalItem] = []
     for msg in messages:
@@ -124,6 +148,18 @@ class OpenAIParser(Parser):
         req.max_tokens = int(data.get("max_tokens",
                                       data.get("max_completion_tokens", 16)))
         req.temperature = float(data.get("temperature", 0.0))
+        err = _sampling_into(req, data.get("top_p"), data.get("top_k"),
+                             data.get("seed"), "top_p", "top_k")
+        if err:
+            return ParseResult(error=err)
+        lp = data.get("logprobs")
+        if isinstance(lp, bool) or lp is None:
+            req.logprobs = bool(lp)
+        elif isinstance(lp, int) and lp >= 1:
+            req.logprobs = True     # legacy completions form: a count
+        elif lp != 0:
+            return ParseResult(
+                error="logprobs must be a boolean or an integer >= 0")
         if isinstance(data.get("stop_token_ids"), list):
             req.stop_token_ids = [int(t) for t in data["stop_token_ids"]]
         req.streaming = bool(data.get("stream", False))
@@ -200,6 +236,10 @@ class VertexAIParser(Parser):
         gen_cfg = data.get("generationConfig") or {}
         req.max_tokens = int(gen_cfg.get("maxOutputTokens", 16))
         req.temperature = float(gen_cfg.get("temperature", 0.0))
+        err = _sampling_into(req, gen_cfg.get("topP"), gen_cfg.get("topK"),
+                             gen_cfg.get("seed"), "topP", "topK")
+        if err:
+            return ParseResult(error=err)
         _headers_into(req, headers)
         return ParseResult(request=req)
 

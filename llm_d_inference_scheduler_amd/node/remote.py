@@ -107,6 +107,8 @@ class RemoteForwarder:
             "prompt_tokens": req.prompt_tokens,
             "max_tokens": req.max_tokens,
             "temperature": req.temperature,
+            "top_k": req.top_k, "top_p": req.top_p, "seed": req.seed,
+            "logprobs": req.logprobs,
             "stop_token_ids": req.stop_token_ids,
             "priority": req.priority,
             "stream": bool(req.streaming),
@@ -131,7 +133,8 @@ class RemoteForwarder:
                             e2e_ms=u.get("e2e_ms")),
                 tokens=resp.get("tokens", []),
                 finish_reason=resp.get("finish_reason", "length"),
-                error=resp.get("error", ""))
+                error=resp.get("error", ""),
+                token_logprobs=resp.get("token_logprobs"))
         except Exception as e:
             log.error("remote forward failed", url=url, err=str(e))
             comp = Completion(request_id=request_id, usage=Usage(),
@@ -166,7 +169,8 @@ class RemoteForwarder:
                             e2e_ms=u.get("e2e_ms")),
                 tokens=final.get("tokens", []),
                 finish_reason=final.get("finish_reason", "length"),
-                error=final.get("error", ""))
+                error=final.get("error", ""),
+                token_logprobs=final.get("token_logprobs"))
         except Exception as e:
             log.error("remote stream failed", url=url, err=str(e))
             comp = Completion(request_id=request_id, usage=Usage(),

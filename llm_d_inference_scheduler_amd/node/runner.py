@@ -159,6 +159,8 @@ class Completion:
     tokens: List[int] = field(default_factory=list)
     finish_reason: str = "length"   # length | stop
     error: str = ""
+    # one logprob per entry of tokens, for a logprobs=True request
+    token_logprobs: Optional[List[float]] = None
 
 
 class NodeRunner:
@@ -638,6 +640,8 @@ class NodeRunner:
                    "stop": req.stop_token_ids,
                    "max_tokens": max_tokens,
                    "temperature": req.temperature,
+                   "top_k": req.top_k, "top_p": req.top_p,
+                   "seed": req.seed, "logprobs": req.logprobs,
                    "is_embedding": req.is_embedding,
                    "stream": req.streaming,
                    "cached": self._cached_tokens(decision, decode_rank),
@@ -724,6 +728,8 @@ class NodeRunner:
         req = EngineRequest(
             request_id=m["req_id"], prompt_tokens=list(m["tokens"]),
             max_tokens=m["max_tokens"], temperature=m["temperature"],
+            top_k=m.get("top_k", 0), top_p=m.get("top_p", 1.0),
+            seed=m.get("seed"), logprobs=m.get("logprobs", False),
             is_embedding=m.get("is_embedding", False),
             cached_tokens=m.get("cached", 0),
             priority=m.get("priority", 0),
@@ -754,6 +760,8 @@ class NodeRunner:
             decode_req = EngineRequest(
                 request_id=m["req_id"], prompt_tokens=list(m["tokens"]),
                 max_tokens=m["max_tokens"], temperature=m["temperature"],
+                top_k=m.get("top_k", 0), top_p=m.get("top_p", 1.0),
+                seed=m.get("seed"), logprobs=m.get("logprobs", False),
                 cached_tokens=m.get("cached", 0),
                 priority=m.get("priority", 0),
                 stop_token_ids=m.get("stop"),
@@ -808,6 +816,8 @@ class NodeRunner:
             # chunked decode: accumulate and either continue or finalize
             # with cumulative usage (decode.go cumulative SSE usage)
             state["tokens"].extend(m.get("tokens", []))
+            if m.get("token_logprobs") is not None:
+                state.setdefault("logprobs", []).extend(m["token_logprobs"])
             if state["first_usage"] is None:
                 state["first_usage"] = usage
             orig = state["orig"]
@@ -820,6 +830,8 @@ class NodeRunner:
                     state["tokens"],
                     max_tokens=orig.max_tokens,
                     temperature=orig.temperature,
+                    top_k=orig.top_k, top_p=orig.top_p, seed=orig.seed,
+                    logprobs=orig.logprobs,
                     stop_token_ids=orig.stop_token_ids,
                     streaming=orig.streaming, headers=dict(orig.headers),
                     objective_name=orig.objective_name,
@@ -838,7 +850,8 @@ class NodeRunner:
             self._completions.append(Completion(
                 request_id=m["req_id"], usage=usage,
                 tokens=state["tokens"],
-                finish_reason=m.get("finish_reason", "length"), error=""))
+                finish_reason=m.get("finish_reason", "length"), error="",
+                token_logprobs=state.get("logprobs")))
             return
         self._chunked.pop(m["req_id"], None)
         if self.evictor is not None:
@@ -847,7 +860,8 @@ class NodeRunner:
             request_id=m["req_id"], usage=usage,
             tokens=m.get("tokens", []),
             finish_reason=m.get("finish_reason", "length"),
-            error=m.get("error", "")))
+            error=m.get("error", ""),
+            token_logprobs=m.get("token_logprobs")))
 
     # ---- encode stage (E/PD, E/P/D) ----
     def _run_encoder(self, max_jobs: int = 8) -> None:
@@ -973,7 +987,8 @@ class NodeRunner:
             else:
                 self.engine.admit_transferred(pending["req"], local,
                                               job["seq_len"],
-                                              job["first_token"])
+                                              job["first_token"],
+                                              job.get("first_logprob"))
                 # true TTFT through the hand-off (connector_nixlv2.go
                 # true_ttft_ms span attr): first token is client-visible
                 # only once the decode side adopted the KV
@@ -1025,6 +1040,8 @@ class NodeRunner:
                     "src": self.rank, "dst": decode_rank,
                     "blocks": out.kv_blocks, "seq_len": out.seq_len,
                     "first_token": out.first_token,
+                    "first_logprob": (out.new_logprobs[0]
+                                      if out.new_logprobs else None),
                     "ttft_ms": out.ttft_ms,
                     "kv_scales_id": self.engine.pool.scales_id})
             elif out.kind == "embedding" and out.finished:
@@ -1061,6 +1078,8 @@ class NodeRunner:
                "tokens": out.all_tokens or [],
                "ttft_ms": out.ttft_ms, "tpot_ms": out.tpot_ms,
                "e2e_ms": out.e2e_ms, "error": out.error}
+        if out.all_logprobs is not None:
+            msg["token_logprobs"] = list(out.all_logprobs)
         if self.is_router:
             self._handle_done(msg)
         else:

@@ -133,6 +133,19 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor,
                                    seq_meta, tiles, scale, k_scale, v_scale)
 
 
+def sample(logits: torch.Tensor, temperature: torch.Tensor,
+           top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
+           pos: torch.Tensor):
+    """Fused sampler (DEVELOPMENT.md "Sampling"): logits [B, V] bf16|fp32 and
+    per-row temperature f32, top_k i32 (0 = off), top_p f32 (1 = off), seed
+    i64 (the bits of a u64) and pos i32 -> (tokens i64, logprobs f32,
+    n_kept i32, threshold f32), all [B] on the logits' device."""
+    if _use_hip(logits):
+        return _ext.sample(logits.contiguous(), temperature, top_k, top_p,
+                           seed, pos)
+    return ref.sample(logits, temperature, top_k, top_p, seed, pos)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

@@ -128,3 +128,125 @@ def gather_prefix(k_cache: torch.Tensor, v_cache: torch.Tensor,
     k = k.reshape(S, k.shape[2], k.shape[3])[:seq_len]
     v = v.reshape(S, v.shape[2], v.shape[3])[:seq_len]
     return k, v
+
+
+# ---- sampler (contract: DEVELOPMENT.md "Sampling") -------------------------
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+_MASS_SCALE = 4294967296.0          # masses are summed in 2^-32 fixed point
+_U_MAX = 1.0 - 2.0 ** -24           # largest fp32 below 1
+
+
+def philox4x32_10(counter: torch.Tensor, key) -> torch.Tensor:
+    """Philox4x32-10 over a batch of counters. counter: [..., 4] int64 holding
+    32-bit words; key: (k0, k1) python ints. Returns [..., 4] int64 words.
+    32x32->64 products wrap in int64, which keeps their bit pattern."""
+    c0, c1, c2, c3 = (counter[..., i] & _M32 for i in range(4))
+    k0, k1 = int(key[0]) & _M32, int(key[1]) & _M32
+    for _ in range(10):
+        p0 = c0 * _PHILOX_M0
+        p1 = c2 * _PHILOX_M1
+        n0 = ((p1 >> 32) & _M32) ^ c1 ^ k0
+        n2 = ((p0 >> 32) & _M32) ^ c3 ^ k1
+        c1, c3 = p1 & _M32, p0 & _M32
+        c0, c2 = n0, n2
+        k0 = (k0 + _PHILOX_W0) & _M32
+        k1 = (k1 + _PHILOX_W1) & _M32
+    return torch.stack([c0, c1, c2, c3], dim=-1)
+
+
+def gumbel_noise(idx: torch.Tensor, seed: int, pos: int) -> torch.Tensor:
+    """g_i of the sampling contract for vocabulary indices idx (int64)."""
+    ctr = torch.zeros((idx.shape[0], 4), dtype=torch.int64)
+    ctr[:, 0] = idx >> 2
+    ctr[:, 1] = int(pos) & _M32
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    words = philox4x32_10(ctr, (seed & _M32, seed >> 32))
+    x = words.gather(1, (idx & 3).unsqueeze(1)).squeeze(1)
+    u = ((x >> 8).to(torch.float32) + 0.5) * torch.tensor(
+        2.0 ** -24, dtype=torch.float32)
+    u = u.clamp(max=_U_MAX)
+    return -torch.log(-torch.log(u))
+
+
+def _sample_row(l: torch.Tensor, T: float, k: int, p: float, seed: int,
+                pos: int):
+    """One row of sample(); l is fp32 [V]. Returns (token, logprob, n_kept,
+    threshold, detail)."""
+    V = l.shape[0]
+    f32 = torch.float32
+    M = l.max()
+    lse = M + torch.log(torch.exp(l - M).sum(dtype=f32))
+    detail = {"score_gap": float("inf"), "max_abs_z": 0.0,
+              "mass_margin": float("inf")}
+    T32 = torch.tensor(T, dtype=f32)
+    if not T32 > 0:
+        tok = int(torch.nonzero(l == M)[0])
+        return tok, float(l[tok] - lse), V, float("-inf"), detail
+    inv = torch.tensor(1.0, dtype=f32) / T32
+    z = l * inv
+    m = z.max()
+    tau = torch.tensor(float("-inf"), dtype=f32)
+    if 0 < k < V:
+        tau = torch.topk(z, k).values[-1]
+    p32 = torch.tensor(p, dtype=f32)
+    if p32 < 1:
+        kept_k = torch.nonzero(z >= tau).squeeze(1)
+        zk = z[kept_k]
+        w = torch.exp(zk - m)
+        q = torch.round(w * _MASS_SCALE).to(torch.int64)
+        order = torch.argsort(zk, descending=True, stable=True)
+        zs, cum = zk[order], torch.cumsum(q[order], dim=0)
+        W = cum[-1]
+        target = p32.double() * W.double()
+        # a value's mass counts every element tied with it: the cumulative
+        # sum at the last element of each run of equal z
+        ends = torch.nonzero(torch.cat(
+            [zs[1:] != zs[:-1], torch.tensor([True])])).squeeze(1)
+        cum_end = cum[ends].double()
+        g = int(torch.nonzero(cum_end >= target)[0])
+        tau_p = zs[ends[g]]
+        margin = abs(float(cum_end[g] - target))
+        if g > 0:
+            margin = min(margin, abs(float(target - cum_end[g - 1])))
+        detail["mass_margin"] = margin / float(W)
+        tau = torch.maximum(tau, tau_p)
+    kept = torch.nonzero(z >= tau).squeeze(1)
+    score = z[kept] + gumbel_noise(kept, seed, pos)
+    best = int(torch.argmax(score))         # first maximum = lowest index
+    if score.shape[0] > 1:
+        top2 = torch.topk(score, 2).values
+        detail["score_gap"] = float(top2[0] - top2[1])
+    detail["max_abs_z"] = float(z.abs().max())
+    tok = int(kept[best])
+    return (tok, float(l[tok] - lse), int(kept.shape[0]), float(tau * T32),
+            detail)
+
+
+def sample(logits: torch.Tensor, temperature: torch.Tensor,
+           top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
+           pos: torch.Tensor, details: bool = False):
+    """Temperature / top-k / top-p / seeded Gumbel-max sampling with the
+    sampled token's logprob. logits [B, V] bf16|fp32; temperature, top_p [B]
+    fp32; top_k, pos [B] int32; seed [B] int64 (the bits of a u64).
+    Returns (tokens i64, logprobs f32, n_kept i32, threshold f32), plus a
+    list of per-row dicts with details=True: the gap between the two best
+    perturbed scores, max |z| over the row, and how far (as a share of
+    W) the top-p mass at the boundary is from p*W on either side."""
+    B = logits.shape[0]
+    lf = logits.detach().to("cpu", torch.float32)
+    toks, lps, nks, ths, dets = [], [], [], [], []
+    for r in range(B):
+        tok, lp, nk, th, det = _sample_row(
+            lf[r], float(temperature[r]), int(top_k[r]), float(top_p[r]),
+            int(seed[r]), int(pos[r]))
+        toks.append(tok); lps.append(lp); nks.append(nk); ths.append(th)
+        dets.append(det)
+    dev = logits.device
+    out = (torch.tensor(toks, dtype=torch.int64, device=dev),
+           torch.tensor(lps, dtype=torch.float32, device=dev),
+           torch.tensor(nks, dtype=torch.int32, device=dev),
+           torch.tensor(ths, dtype=torch.float32, device=dev))
+    return out + (dets,) if details else out

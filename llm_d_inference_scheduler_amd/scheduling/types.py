@@ -30,6 +30,10 @@ class LLMRequest:
     prompt_tokens: Optional[List[int]] = None      # set by token-producer
     max_tokens: int = 16
     temperature: float = 0.0
+    top_k: int = 0                  # 0 = off
+    top_p: float = 1.0              # 1.0 = off
+    seed: Optional[int] = None      # u64; None = engine-derived
+    logprobs: bool = False          # return the sampled tokens' logprobs
     stop_token_ids: Optional[List[int]] = None
     streaming: bool = False
     is_embedding: bool = False

@@ -118,19 +118,28 @@ def build_app(service: NodeService,
         text = tok.decode(completion.tokens)
         usage = completion.usage.to_openai()
         created = int(time.time())
+        lps = completion.token_logprobs if req.logprobs else None
+        pieces = [tok.decode([t]) for t in completion.tokens] \
+            if lps is not None else []
         if "chat" in path:
+            choice = {"index": 0, "message":
+                      {"role": "assistant", "content": text},
+                      "finish_reason": completion.finish_reason}
+            if lps is not None:
+                choice["logprobs"] = {"content": [
+                    {"token": p, "logprob": lp}
+                    for p, lp in zip(pieces, lps)]}
             return {"id": f"chatcmpl-{req.request_id}", "object":
                     "chat.completion", "created": created,
-                    "model": req.model,
-                    "choices": [{"index": 0, "message":
-                                 {"role": "assistant", "content": text},
-                                 "finish_reason": completion.finish_reason}],
+                    "model": req.model, "choices": [choice],
                     "usage": usage}
+        choice = {"index": 0, "text": text,
+                  "finish_reason": completion.finish_reason}
+        if lps is not None:
+            choice["logprobs"] = {"tokens": pieces, "token_logprobs": lps}
         return {"id": f"cmpl-{req.request_id}", "object": "text_completion",
                 "created": created, "model": req.model,
-                "choices": [{"index": 0, "text": text,
-                             "finish_reason": completion.finish_reason}],
-                "usage": usage}
+                "choices": [choice], "usage": usage}
 
     def _embedding_response(req, completion):
         return {"object": "list", "model": req.model,
@@ -243,6 +252,9 @@ def build_app(service: NodeService,
             prompt_tokens=body.get("prompt_tokens"),
             max_tokens=int(body.get("max_tokens", 16)),
             temperature=float(body.get("temperature") or 0.0),
+            top_k=int(body.get("top_k") or 0),
+            top_p=float(body.get("top_p") or 1.0),
+            seed=body.get("seed"), logprobs=bool(body.get("logprobs")),
             stop_token_ids=body.get("stop_token_ids"),
             streaming=bool(body.get("stream", False)),
             priority=int(body.get("priority", 0)))
@@ -265,6 +277,8 @@ def build_app(service: NodeService,
                          "finish_reason": (comp.finish_reason
                                            if comp else "length"),
                          "error": comp.error if comp else "lost",
+                         "token_logprobs": (comp.token_logprobs
+                                            if comp else None),
                          "usage": {"prompt_tokens": u.prompt_tokens,
                                    "completion_tokens": u.completion_tokens,
                                    "cached_tokens": u.cached_tokens,
@@ -283,6 +297,7 @@ def build_app(service: NodeService,
         return {"tokens": completion.tokens,
                 "finish_reason": completion.finish_reason,
                 "error": completion.error,
+                "token_logprobs": completion.token_logprobs,
                 "usage": {"prompt_tokens": u.prompt_tokens,
                           "completion_tokens": u.completion_tokens,
                           "cached_tokens": u.cached_tokens,

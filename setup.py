@@ -37,6 +37,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/paged_attention.hip",
         "csrc/hip/flash_prefill.hip",
         "csrc/hip/flash_prefill_glds.hip",
+        "csrc/hip/sampler.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],
