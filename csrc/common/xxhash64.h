@@ -2,7 +2,7 @@
 // implemented from the xxHash specification) usable from host C++ and HIP
 // device code. This is the single definition of the prefix-cache block hash
 // chain used by the router: the CPU path (csrc/router) and the gfx950 kernels
-// (csrc/hip/prefix_hash.hip) both include this header, so CPU==GPU bitwise.
+// (csrc/hip/prefix_kernels.hip) both include this header, so CPU==GPU bitwise.
 //
 // Capability parity: reference `approximateprefix/hashing.go:35-99` chains
 // xxhash64 over prompt character blocks. We chain over token-id blocks

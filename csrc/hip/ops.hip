@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 #include "flash_prefill.h"
 
 #define CHECK_HIP(expr)                                                    \
@@ -21,7 +23,8 @@ extern "C" {
 hipError_t lds_hash_prompts(const int32_t*, const int64_t*, int, int, int,
                             uint64_t, uint64_t*, int32_t*, hipStream_t);
 hipError_t lds_table_update(uint64_t*, unsigned long long*, uint32_t,
-                            const uint64_t*, int64_t, int, int, hipStream_t);
+                            const uint64_t*, int64_t, int, int, unsigned int*,
+                            hipStream_t);
 hipError_t lds_match_longest(const uint64_t*, const unsigned long long*,
                              uint32_t, const uint64_t*, const int32_t*, int,
                              int, int, int32_t*, hipStream_t);
@@ -80,6 +83,32 @@ hipStream_t cur_stream() {
 
 // ---- prefix-cache kernels ----
 
+// Every argument is checked here, on the host, before anything is launched:
+// the kernels trust their sizes.
+
+// keys/masks of the device table: uint64, equally long, 2^k slots.
+void check_table(const torch::Tensor& keys, const torch::Tensor& masks) {
+  CHECK_GPU(keys); CHECK_GPU(masks);
+  TORCH_CHECK(keys.scalar_type() == at::kUInt64 &&
+              masks.scalar_type() == at::kUInt64,
+              "table keys and masks must be uint64");
+  TORCH_CHECK(masks.device() == keys.device(),
+              "table keys and masks must be on one device");
+  TORCH_CHECK(keys.numel() == masks.numel(), "table keys (", keys.numel(),
+              ") and masks (", masks.numel(), ") must be equally long");
+  int64_t cap = keys.numel();
+  // 2^31 at most: the kernels count probes in a uint32 up to cap-1
+  TORCH_CHECK(cap >= 1 && cap <= (int64_t(1) << 31) && (cap & (cap - 1)) == 0,
+              "table cap must be 2^k, 1 <= cap <= 2^31");
+}
+
+void check_hashes(const torch::Tensor& hashes, const torch::Tensor& keys) {
+  CHECK_GPU(hashes);
+  TORCH_CHECK(hashes.scalar_type() == at::kUInt64, "hashes must be uint64");
+  TORCH_CHECK(hashes.device() == keys.device(),
+              "hashes must be on the table's device");
+}
+
 std::vector<torch::Tensor> hash_prompts(torch::Tensor tokens,
                                         torch::Tensor offsets,
                                         int64_t block_tokens,
@@ -87,6 +116,14 @@ std::vector<torch::Tensor> hash_prompts(torch::Tensor tokens,
   CHECK_GPU(tokens);
   CHECK_GPU(offsets);
   TORCH_CHECK(tokens.dtype() == torch::kInt32 && offsets.dtype() == torch::kInt64);
+  TORCH_CHECK(offsets.device() == tokens.device(),
+              "tokens and offsets must be on one device");
+  TORCH_CHECK(block_tokens >= 1 && block_tokens <= INT_MAX,
+              "block_tokens must be >= 1, got ", block_tokens);
+  TORCH_CHECK(max_blocks >= 1 && max_blocks <= INT_MAX,
+              "max_blocks must be >= 1, got ", max_blocks);
+  TORCH_CHECK(offsets.numel() >= 1,
+              "offsets must hold R+1 >= 1 values (request starts and the end)");
   int n_req = (int)offsets.size(0) - 1;
   auto hashes = torch::zeros({n_req, max_blocks},
                              tokens.options().dtype(torch::kUInt64));
@@ -98,20 +135,45 @@ std::vector<torch::Tensor> hash_prompts(torch::Tensor tokens,
   return {hashes, counts};
 }
 
+// dropped: optional one-element int32 counter on the table's device; an
+// insert that finds no slot in cap probes adds 1 to it.
 void table_update(torch::Tensor keys, torch::Tensor masks,
-                  torch::Tensor hashes, int64_t endpoint, bool is_remove) {
-  CHECK_GPU(keys); CHECK_GPU(masks); CHECK_GPU(hashes);
-  TORCH_CHECK((keys.size(0) & (keys.size(0) - 1)) == 0, "table cap must be 2^k");
+                  torch::Tensor hashes, int64_t endpoint, bool is_remove,
+                  c10::optional<torch::Tensor> dropped) {
+  check_table(keys, masks);
+  check_hashes(hashes, keys);
+  TORCH_CHECK(endpoint >= 0 && endpoint < 64,
+              "endpoint must be in [0, 64), got ", endpoint);
+  unsigned int* dropped_ptr = nullptr;
+  if (dropped.has_value()) {
+    CHECK_GPU(*dropped);
+    TORCH_CHECK(dropped->scalar_type() == at::kInt && dropped->numel() == 1 &&
+                dropped->device() == keys.device(),
+                "dropped must be one int32 on the table's device");
+    dropped_ptr = (unsigned int*)dropped->data_ptr<int32_t>();
+  }
   CHECK_HIP(lds_table_update(
       (uint64_t*)keys.data_ptr(), (unsigned long long*)masks.data_ptr(),
       (uint32_t)(keys.size(0) - 1), (const uint64_t*)hashes.data_ptr(),
-      hashes.numel(), (int)endpoint, is_remove ? 1 : 0, cur_stream()));
+      hashes.numel(), (int)endpoint, is_remove ? 1 : 0, dropped_ptr,
+      cur_stream()));
 }
 
 torch::Tensor match_longest(torch::Tensor keys, torch::Tensor masks,
                             torch::Tensor hashes, torch::Tensor counts,
                             int64_t n_endpoints) {
-  CHECK_GPU(keys); CHECK_GPU(masks); CHECK_GPU(hashes); CHECK_GPU(counts);
+  check_table(keys, masks);
+  check_hashes(hashes, keys);
+  CHECK_GPU(counts);
+  TORCH_CHECK(hashes.dim() == 2, "hashes must be [R, max_blocks]");
+  TORCH_CHECK(hashes.size(1) <= INT_MAX, "hashes rows are too long");
+  TORCH_CHECK(counts.scalar_type() == at::kInt &&
+              counts.device() == keys.device(),
+              "counts must be int32 on the table's device");
+  TORCH_CHECK(counts.numel() == hashes.size(0), "counts (", counts.numel(),
+              ") must hold one value per hashes row (", hashes.size(0), ")");
+  TORCH_CHECK(n_endpoints >= 1 && n_endpoints <= 64,
+              "n_endpoints must be in [1, 64], got ", n_endpoints);
   int n_req = (int)hashes.size(0);
   auto out = torch::zeros({n_req, n_endpoints},
                           hashes.options().dtype(torch::kInt32));
@@ -398,7 +460,10 @@ std::vector<torch::Tensor> sample(torch::Tensor logits,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X gfx950 kernels: prefix-cache hashing/match, paged KV, decode attention";
   m.def("hash_prompts", &hash_prompts, "batched chained block hashing");
-  m.def("table_update", &table_update, "device prefix table insert/remove");
+  m.def("table_update", &table_update, "device prefix table insert/remove",
+        py::arg("keys"), py::arg("masks"), py::arg("hashes"),
+        py::arg("endpoint"), py::arg("is_remove"),
+        py::arg("dropped") = py::none());
   m.def("match_longest", &match_longest, "device longest-prefix match");
   m.def("rmsnorm", &rmsnorm, py::arg("x"), py::arg("w"), py::arg("eps"),
         py::arg("residual") = py::none());

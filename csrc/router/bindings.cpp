@@ -29,6 +29,10 @@ py::array_t<uint64_t> py_hash_tokens(py::array_t<int32_t, py::array::c_style | p
   return out;
 }
 
+py::array_t<uint64_t> u64_array(const std::vector<uint64_t>& v) {
+  return py::array_t<uint64_t>((py::ssize_t)v.size(), v.data());
+}
+
 uint64_t py_model_seed(const std::string& model, const std::string& salt) {
   return model_seed(model.data(), model.size(), salt.data(), salt.size());
 }
@@ -71,10 +75,33 @@ PYBIND11_MODULE(_router_core, m) {
              return out;
            },
            py::arg("hashes"), py::arg("num_endpoints"))
+      .def("add_evicting",
+           [](PrefixIndex& self, int endpoint,
+              py::array_t<uint64_t, py::array::c_style | py::array::forcecast> hashes) {
+             std::vector<uint64_t> ev;
+             {
+               py::gil_scoped_release rel;
+               ev = self.add_evicting(endpoint, hashes.data(), hashes.size());
+             }
+             return u64_array(ev);
+           },
+           py::arg("endpoint"), py::arg("hashes"))
+      .def("endpoint_hashes",
+           [](const PrefixIndex& self, int endpoint) {
+             return u64_array(self.endpoint_hashes(endpoint));
+           },
+           py::arg("endpoint"))
       .def("remove_endpoint", &PrefixIndex::remove_endpoint)
       .def("size", &PrefixIndex::size)
       .def("endpoint_size", &PrefixIndex::endpoint_size)
-      .def("set_capacity", &PrefixIndex::set_capacity)
+      .def("set_capacity",
+           [](PrefixIndex& self, int64_t cap) {
+             py::list out;
+             for (auto& [e, ev] : self.set_capacity(cap))
+               out.append(py::make_tuple(e, u64_array(ev)));
+             return out;
+           },
+           py::arg("capacity"))
       .def("capacity", &PrefixIndex::capacity);
 
   py::class_<ProfileRunner>(m, "ProfileRunner")

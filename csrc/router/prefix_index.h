@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <cstring>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 #include <deque>
 #include <shared_mutex>
@@ -65,44 +66,16 @@ class PrefixIndex {
   // Returns number of evicted blocks.
   int64_t add(int endpoint, const uint64_t* hashes, int64_t n) {
     std::unique_lock lk(mu_);
-    if (endpoint < 0 || endpoint >= kMaxEndpoints) return 0;
-    LruList& lru = lrus_[endpoint];
-    const uint64_t bit = 1ULL << endpoint;
-    for (int64_t i = 0; i < n; ++i) {
-      uint64_t h = hashes[i];
-      auto it = lru.pos.find(h);
-      if (it != lru.pos.end()) {
-        lru.unlink(it->second);
-        lru.push_front(it->second);
-        continue;
-      }
-      int32_t slot;
-      if (!lru.free.empty()) { slot = lru.free.front(); lru.free.pop_front(); }
-      else { slot = (int32_t)lru.pool.size(); lru.pool.emplace_back(); }
-      lru.pool[slot].hash = h;
-      lru.pool[slot].live = true;
-      lru.push_front(slot);
-      lru.pos.emplace(h, slot);
-      lru.size++;
-      map_[h].mask |= bit;
-    }
-    // evict over capacity (oldest first)
-    int64_t evicted = 0;
-    while (lru.size > cap_ && lru.tail >= 0) {
-      int32_t victim = lru.tail;
-      uint64_t h = lru.pool[victim].hash;
-      lru.unlink(victim);
-      lru.pool[victim].live = false;
-      lru.free.push_back(victim);
-      lru.pos.erase(h);
-      lru.size--;
-      auto mit = map_.find(h);
-      if (mit != map_.end()) {
-        mit->second.mask &= ~bit;
-        if (mit->second.mask == 0) map_.erase(mit);
-      }
-      evicted++;
-    }
+    return add_locked(endpoint, hashes, n, nullptr);
+  }
+
+  // add() that also reports which hashes left `endpoint`'s LRU, oldest
+  // first, so a mirror of this index (ops/prefix.py) can drop them too.
+  std::vector<uint64_t> add_evicting(int endpoint, const uint64_t* hashes,
+                                     int64_t n) {
+    std::unique_lock lk(mu_);
+    std::vector<uint64_t> evicted;
+    add_locked(endpoint, hashes, n, &evicted);
     return evicted;
   }
 
@@ -156,13 +129,83 @@ class PrefixIndex {
     std::shared_lock lk(mu_);
     return lrus_[endpoint].size;
   }
-  void set_capacity(int64_t cap) {
+  // Hashes `endpoint` currently holds, most recent first.
+  std::vector<uint64_t> endpoint_hashes(int endpoint) const {
+    std::shared_lock lk(mu_);
+    std::vector<uint64_t> out;
+    if (endpoint < 0 || endpoint >= kMaxEndpoints) return out;
+    const LruList& lru = lrus_[endpoint];
+    out.reserve((size_t)lru.size);
+    for (int32_t i = lru.head; i >= 0; i = lru.pool[i].next)
+      out.push_back(lru.pool[i].hash);
+    return out;
+  }
+  // Shrinking evicts at once. Returns (endpoint, hashes evicted oldest
+  // first) for every endpoint that lost blocks.
+  std::vector<std::pair<int, std::vector<uint64_t>>> set_capacity(int64_t cap) {
     std::unique_lock lk(mu_);
     cap_ = cap;
+    std::vector<std::pair<int, std::vector<uint64_t>>> out;
+    for (int e = 0; e < kMaxEndpoints; ++e) {
+      if (lrus_[e].size <= cap_) continue;
+      out.emplace_back(e, std::vector<uint64_t>{});
+      evict_over_capacity(e, &out.back().second);
+    }
+    return out;
   }
   int64_t capacity() const { return cap_; }
 
  private:
+  int64_t add_locked(int endpoint, const uint64_t* hashes, int64_t n,
+                     std::vector<uint64_t>* evicted_out) {
+    if (endpoint < 0 || endpoint >= kMaxEndpoints) return 0;
+    LruList& lru = lrus_[endpoint];
+    const uint64_t bit = 1ULL << endpoint;
+    for (int64_t i = 0; i < n; ++i) {
+      uint64_t h = hashes[i];
+      auto it = lru.pos.find(h);
+      if (it != lru.pos.end()) {
+        lru.unlink(it->second);
+        lru.push_front(it->second);
+        continue;
+      }
+      int32_t slot;
+      if (!lru.free.empty()) { slot = lru.free.front(); lru.free.pop_front(); }
+      else { slot = (int32_t)lru.pool.size(); lru.pool.emplace_back(); }
+      lru.pool[slot].hash = h;
+      lru.pool[slot].live = true;
+      lru.push_front(slot);
+      lru.pos.emplace(h, slot);
+      lru.size++;
+      map_[h].mask |= bit;
+    }
+    return evict_over_capacity(endpoint, evicted_out);
+  }
+
+  // evict over capacity (oldest first)
+  int64_t evict_over_capacity(int endpoint, std::vector<uint64_t>* evicted_out) {
+    LruList& lru = lrus_[endpoint];
+    const uint64_t bit = 1ULL << endpoint;
+    int64_t evicted = 0;
+    while (lru.size > cap_ && lru.tail >= 0) {
+      int32_t victim = lru.tail;
+      uint64_t h = lru.pool[victim].hash;
+      lru.unlink(victim);
+      lru.pool[victim].live = false;
+      lru.free.push_back(victim);
+      lru.pos.erase(h);
+      lru.size--;
+      auto mit = map_.find(h);
+      if (mit != map_.end()) {
+        mit->second.mask &= ~bit;
+        if (mit->second.mask == 0) map_.erase(mit);
+      }
+      if (evicted_out) evicted_out->push_back(h);
+      evicted++;
+    }
+    return evicted;
+  }
+
   mutable std::shared_mutex mu_;
   int64_t cap_;
   std::unordered_map<uint64_t, Entry> map_;

@@ -7,6 +7,7 @@
 #include <cassert>
 #include <cstdio>
 #include <random>
+#include <set>
 #include <vector>
 
 #include "../prefix_index.h"
@@ -39,12 +40,87 @@ static void exercise_prefix_index(std::mt19937_64& rng) {
     }
     assert(ix.size() >= 0);
   }
-  ix.set_capacity(4);   // shrink is applied lazily by the next add
+  ix.set_capacity(4);   // shrinking evicts at once
   for (int e = 0; e < 8; ++e) {
+    assert(ix.endpoint_size(e) <= 4);
     uint64_t one = 9999;
     ix.add(e, &one, 1);
     assert(ix.endpoint_size(e) <= 4);
   }
+}
+
+// add_evicting / endpoint_hashes / shrinking set_capacity against a mirror
+// kept only from what they report: per endpoint, the set of hashes added
+// minus the hashes reported evicted. If a report misses an eviction (or
+// names a hash that stayed) the mirror and endpoint_hashes() part ways.
+static void exercise_prefix_mirror(std::mt19937_64& rng) {
+  constexpr int kEps = 6;
+  PrefixIndex ix(16);
+  std::vector<std::set<uint64_t>> mirror(kEps);
+  std::uniform_int_distribution<uint64_t> h(0, 120);
+  std::uniform_int_distribution<int> ep(0, kEps - 1), n(1, 40), capd(1, 24);
+  auto check = [&](int e) {
+    std::vector<uint64_t> live = ix.endpoint_hashes(e);
+    assert((int64_t)live.size() == ix.endpoint_size(e));
+    assert((int64_t)live.size() <= ix.capacity());
+    std::set<uint64_t> s(live.begin(), live.end());
+    assert(s.size() == live.size());
+    assert(s == mirror[e]);
+  };
+  for (int it = 0; it < 4000; ++it) {
+    int e = ep(rng);
+    switch (it % 7) {
+      case 0: case 1: case 2: case 3: {
+        std::vector<uint64_t> hashes(n(rng));
+        for (auto& x : hashes) x = h(rng);
+        std::vector<uint64_t> before = ix.endpoint_hashes(e);
+        std::vector<uint64_t> ev =
+            ix.add_evicting(e, hashes.data(), (int64_t)hashes.size());
+        for (uint64_t x : hashes) mirror[e].insert(x);
+        for (uint64_t x : ev) {
+          assert(mirror[e].count(x));  // reported once, and was resident
+          mirror[e].erase(x);
+        }
+        // oldest first: hashes resident before the call that are reported
+        // (and were not touched again by it) leave in LRU order, tail first
+        std::set<uint64_t> touched(hashes.begin(), hashes.end());
+        size_t k = 0;
+        for (auto rit = before.rbegin(); rit != before.rend(); ++rit) {
+          if (touched.count(*rit)) continue;
+          if (k < ev.size() && ev[k] == *rit) ++k; else break;
+        }
+        for (size_t j = k; j < ev.size(); ++j) assert(touched.count(ev[j]));
+        check(e);
+        break;
+      }
+      case 4: {
+        for (auto& [ee, ev] : ix.set_capacity(capd(rng))) {
+          assert(!ev.empty());
+          for (uint64_t x : ev) {
+            assert(mirror[ee].count(x));
+            mirror[ee].erase(x);
+          }
+        }
+        for (int ee = 0; ee < kEps; ++ee) check(ee);
+        break;
+      }
+      case 5:
+        ix.remove_endpoint(e);
+        mirror[e].clear();
+        check(e);
+        break;
+      default: {
+        // the hash map agrees with the LRUs: a one-hash query matches
+        // exactly the endpoints whose mirror holds it
+        uint64_t q = h(rng);
+        std::vector<int32_t> counts(kEps);
+        ix.match_longest(&q, 1, kEps, counts.data());
+        for (int ee = 0; ee < kEps; ++ee)
+          assert(counts[ee] == (int)mirror[ee].count(q));
+      }
+    }
+  }
+  assert(ix.endpoint_hashes(-1).empty() && ix.endpoint_hashes(64).empty());
 }
 
 template <typename Q>
@@ -107,6 +183,7 @@ static void exercise_runner(std::mt19937_64& rng) {
 int main() {
   std::mt19937_64 rng(42);
   exercise_prefix_index(rng);
+  exercise_prefix_mirror(rng);
   exercise_queue<ListQueue>(rng);
   exercise_queue<MaxMinHeap>(rng);
   exercise_runner(rng);

@@ -556,8 +556,9 @@ class NodeRunner:
             self._emit_assignment(req, decision)
 
     def _gpu_prefix_batch(self, batch: List[LLMRequest]):
-        """One hash_prompts + one match_longest launch for the whole
-        admission batch (SURVEY.md §2.6 MI355X mapping). Returns per-request
+        """One hash_prompts launch per model seed in the batch + one
+        match_longest launch for the whole admission batch (SURVEY.md §2.6
+        MI355X mapping; ops.prefix.batch_match). Returns per-request
         precomputed-attribute dicts, or None to use the host path."""
         # small admission batches route through the C++ host index: the GPU
         # batch path's D2H sync would stall routing behind the whole queued
@@ -568,16 +569,13 @@ class NodeRunner:
             return None
         from ..datalayer.attributes import (PREFIX_CACHE_MATCH_INFO as KEY,
                                             PrefixCacheMatchInfo)
+        from ..ops.prefix import batch_match
         ap = self._approx
-        seed0 = ap._seed(batch[0].target_model or batch[0].model)
-        hashes_dev, counts_dev = self._gpu_prefix.hash_prompts_batch(
-            [r.prompt_tokens for r in batch], ap.block_size, ap.max_blocks,
-            seed0)
         n_eps = len(self.topology.ranks)
-        match = self._gpu_prefix.match_batch(hashes_dev, counts_dev, n_eps)
-        match = match.cpu().numpy()
-        counts = counts_dev.cpu().numpy()
-        hashes = hashes_dev.cpu().numpy()
+        match, counts, hashes = batch_match(
+            self._gpu_prefix, [r.prompt_tokens for r in batch],
+            [ap._seed(r.target_model or r.model) for r in batch],
+            ap.block_size, ap.max_blocks, n_eps)
         out = []
         for i in range(len(batch)):
             info = PrefixCacheMatchInfo(total_blocks=int(counts[i]),

@@ -250,3 +250,244 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor,
            torch.tensor(nks, dtype=torch.int32, device=dev),
            torch.tensor(ths, dtype=torch.float32, device=dev))
     return out + (dets,) if details else out
+
+
+# ---- prefix-cache kernels (contract: DEVELOPMENT.md "Prefix-cache tests") --
+#
+# A second implementation of csrc/common/xxhash64.h and of the device table
+# in csrc/hip/prefix_kernels.hip, in Python integers masked to 64 bits. It
+# shares no code with the C++ core (`_router_core.hash_tokens`), so the two
+# check each other. PrefixModel's small methods are the places where the
+# kernels can go wrong; tests/test_prefix_cases.py overrides them one at a
+# time to prove that the test cases notice.
+
+_M64 = 0xFFFFFFFFFFFFFFFF
+_XP1 = 0x9E3779B185EBCA87
+_XP2 = 0xC2B2AE3D27D4EB4F
+_XP3 = 0x165667B19E3779F9
+_XP4 = 0x85EBCA77C2B2AE63
+_XP5 = 0x27D4EB2F165667C5
+
+
+def _rotl64(x: int, r: int) -> int:
+    return ((x << r) | (x >> (64 - r))) & _M64
+
+
+def _xxh_round(acc: int, inp: int) -> int:
+    return (_rotl64((acc + inp * _XP2) & _M64, 31) * _XP1) & _M64
+
+
+def _xxh_merge(acc: int, val: int) -> int:
+    return ((acc ^ _xxh_round(0, val)) * _XP1 + _XP4) & _M64
+
+
+def xxh64(data: bytes, seed: int) -> int:
+    """XXH64 of `data` from the xxHash specification."""
+    n, p = len(data), 0
+    seed &= _M64
+
+    def rd(k):
+        return int.from_bytes(data[p:p + k], "little")
+
+    if n >= 32:
+        v = [(seed + _XP1 + _XP2) & _M64, (seed + _XP2) & _M64, seed,
+             (seed - _XP1) & _M64]
+        while p + 32 <= n:
+            for i in range(4):
+                v[i] = _xxh_round(v[i], rd(8))
+                p += 8
+        h = (_rotl64(v[0], 1) + _rotl64(v[1], 7) + _rotl64(v[2], 12) +
+             _rotl64(v[3], 18)) & _M64
+        for x in v:
+            h = _xxh_merge(h, x)
+    else:
+        h = (seed + _XP5) & _M64
+    h = (h + n) & _M64
+    while p + 8 <= n:
+        h ^= _xxh_round(0, rd(8))
+        h = (_rotl64(h, 27) * _XP1 + _XP4) & _M64
+        p += 8
+    if p + 4 <= n:
+        h ^= (rd(4) * _XP1) & _M64
+        h = (_rotl64(h, 23) * _XP2 + _XP3) & _M64
+        p += 4
+    while p < n:
+        h ^= (data[p] * _XP5) & _M64
+        h = (_rotl64(h, 11) * _XP1) & _M64
+        p += 1
+    h ^= h >> 33
+    h = (h * _XP2) & _M64
+    h ^= h >> 29
+    h = (h * _XP3) & _M64
+    h ^= h >> 32
+    return h
+
+
+def _req(cond: bool, msg: str) -> None:
+    # the extension rejects bad arguments with TORCH_CHECK -> RuntimeError
+    if not cond:
+        raise RuntimeError(msg)
+
+
+class PrefixModel:
+    """hash_prompts / table_update / match_longest with the extension's
+    signatures and tensor layouts, on CPU tensors.
+
+    Device table: keys[cap] and masks[cap] uint64, cap = 2^k. Key 0 means
+    empty, so hash 0 is stored as 1 (hashes 0 and 1 share one entry). The
+    home slot is key & (cap-1); probing is linear and wraps; a removed key
+    keeps its slot with mask 0; an insert that finds no slot in cap probes
+    is dropped and counted."""
+
+    # -- hashing: the chain of csrc/common/xxhash64.h --
+    def content_hash(self, block: bytes, seed0: int) -> int:
+        return xxh64(block, seed0)
+
+    def chain_start(self, seed0: int) -> int:
+        return seed0
+
+    def chain_hash(self, content: int, prev: int) -> int:
+        return xxh64(content.to_bytes(8, "little") + prev.to_bytes(8, "little"),
+                     0)
+
+    def hash_prompts(self, tokens, offsets, block_tokens, max_blocks, seed0):
+        _req(tokens.dtype == torch.int32 and offsets.dtype == torch.int64,
+             "tokens must be int32 and offsets int64")
+        _req(block_tokens >= 1, "block_tokens must be >= 1")
+        _req(max_blocks >= 1, "max_blocks must be >= 1")
+        _req(offsets.numel() >= 1, "offsets must hold R+1 >= 1 values")
+        import numpy as np
+        tok = tokens.numpy().astype("<i4")
+        off = offsets.numpy()
+        seed0 = int(seed0) & _M64
+        R = off.shape[0] - 1
+        out = np.zeros((R, max_blocks), dtype=np.uint64)
+        counts = np.zeros(R, dtype=np.int32)
+        for r in range(R):
+            beg, end = int(off[r]), int(off[r + 1])
+            n = max(0, min((end - beg) // block_tokens, max_blocks))
+            counts[r] = n
+            prev = self.chain_start(seed0)
+            for b in range(n):
+                lo = beg + b * block_tokens
+                c = self.content_hash(tok[lo:lo + block_tokens].tobytes(),
+                                      seed0)
+                prev = self.chain_hash(c, prev)
+                out[r, b] = prev
+        return torch.from_numpy(out), torch.from_numpy(counts)
+
+    # -- table --
+    def norm_key(self, h: int) -> int:
+        return h if h else 1
+
+    def lookup_key(self, h: int) -> int:
+        return self.norm_key(h)
+
+    def next_slot(self, slot: int, cap: int):
+        """Slot probed after `slot`; None ends the probe."""
+        return (slot + 1) & (cap - 1)
+
+    def same_key(self, stored: int, key: int) -> bool:
+        """Whether an insert of `key` shares the slot holding `stored`."""
+        return stored == key
+
+    def lookup_stops_at(self, stored: int, mask: int) -> bool:
+        """Whether a lookup gives up at a slot holding another key."""
+        return False
+
+    @staticmethod
+    def _check_table(keys, masks, hashes):
+        for t in (keys, masks, hashes):
+            _req(t.dtype == torch.uint64, "keys, masks, hashes must be uint64")
+        _req(keys.numel() == masks.numel(),
+             "table keys and masks must be equally long")
+        cap = keys.numel()
+        _req(cap >= 1 and cap & (cap - 1) == 0, "table cap must be 2^k")
+
+    def table_update(self, keys, masks, hashes, endpoint, is_remove,
+                     dropped=None):
+        self._check_table(keys, masks, hashes)
+        _req(0 <= endpoint < 64, "endpoint must be in [0, 64)")
+        k, m = keys.numpy(), masks.numpy()      # views: updated in place
+        cap = k.shape[0]
+        bit = 1 << endpoint
+        for h in hashes.numpy().reshape(-1).tolist():
+            key = self.norm_key(h)
+            slot = key & (cap - 1)
+            for _ in range(cap):
+                stored = int(k[slot])
+                if is_remove:
+                    if stored == 0:
+                        break
+                    if stored == key:
+                        m[slot] = int(m[slot]) & ~bit & _M64
+                        break
+                elif stored == 0 or self.same_key(stored, key):
+                    k[slot] = key
+                    m[slot] = int(m[slot]) | bit
+                    break
+                slot = self.next_slot(slot, cap)
+                if slot is None:
+                    slot = -1
+                    break
+            else:
+                slot = -1
+            if slot < 0 and not is_remove and dropped is not None:
+                dropped += 1
+
+    def lookup(self, k, m, h: int) -> int:
+        cap = k.shape[0]
+        key = self.lookup_key(h)
+        slot = key & (cap - 1)
+        for _ in range(cap):
+            stored = int(k[slot])
+            if stored == 0:
+                return 0
+            if stored == key:
+                return int(m[slot])
+            if self.lookup_stops_at(stored, int(m[slot])):
+                return 0
+            slot = self.next_slot(slot, cap)
+            if slot is None:
+                return 0
+        return 0
+
+    # -- match --
+    def row_blocks(self, count: int, width: int) -> int:
+        return max(0, min(count, width))
+
+    def next_active(self, active: int, survivors: int, block: int,
+                    full: int) -> int:
+        """Endpoints still matching after `block`."""
+        return survivors
+
+    def match_longest(self, keys, masks, hashes, counts, n_endpoints):
+        self._check_table(keys, masks, hashes)
+        _req(hashes.dim() == 2, "hashes must be [R, max_blocks]")
+        _req(counts.dtype == torch.int32 and
+             counts.numel() == hashes.shape[0],
+             "counts must hold one int32 per hashes row")
+        _req(1 <= n_endpoints <= 64, "n_endpoints must be in [1, 64]")
+        import numpy as np
+        k, m = keys.numpy(), masks.numpy()
+        hs, cs = hashes.numpy(), counts.numpy()
+        R, width = hs.shape
+        full = (1 << n_endpoints) - 1
+        out = np.zeros((R, n_endpoints), dtype=np.int32)
+        for r in range(R):
+            active = full
+            for b in range(self.row_blocks(int(cs[r]), width)):
+                if not active:
+                    break
+                surv = active & self.lookup(k, m, int(hs[r, b]))
+                for e in range(n_endpoints):
+                    if surv >> e & 1:
+                        out[r, e] = b + 1
+                active = self.next_active(active, surv, b, full)
+        return torch.from_numpy(out)
+
+
+_PREFIX_MODEL = PrefixModel()
+hash_prompts = _PREFIX_MODEL.hash_prompts
+table_update = _PREFIX_MODEL.table_update
+match_longest = _PREFIX_MODEL.match_longest

@@ -98,6 +98,11 @@ class ApproxPrefixCacheProducer(DataProducer):
         self._gpu = None  # ops.prefix.GpuPrefixIndex, attached by the node runner
 
     def attach_gpu_index(self, gpu_index) -> None:
+        """Hand `self.index` over to the device mirror. From here on every
+        change to the index (add, endpoint removal, capacity) goes through
+        `gpu_index`, which applies it to `self.index` and to the device
+        table, so the batched device match and `produce` score alike."""
+        gpu_index.adopt_host(self.index)
         self._gpu = gpu_index
 
     def _seed(self, model: str) -> int:
@@ -115,7 +120,10 @@ class ApproxPrefixCacheProducer(DataProducer):
                 if m.cache_block_size > 0:
                     self.block_size = m.cache_block_size
                 self.lru_capacity = m.cache_num_blocks
-                self.index.set_capacity(self.lru_capacity)
+                if self._gpu is not None:
+                    self._gpu.set_capacity(self.lru_capacity)
+                else:
+                    self.index.set_capacity(self.lru_capacity)
                 self._auto_tuned = True
                 return
 
@@ -157,12 +165,16 @@ class ApproxPrefixCacheProducer(DataProducer):
         if hashes is None or not len(hashes):
             return
         for ep in result.all_endpoints():
-            self.index.add(ep.index, hashes)
             if self._gpu is not None:
-                self._gpu.add(ep.index, hashes)
+                self._gpu.add(ep.index, hashes)    # host index + device table
+            else:
+                self.index.add(ep.index, hashes)
 
     def remove_endpoint(self, ep: Endpoint) -> None:
-        self.index.remove_endpoint(ep.index)
+        if self._gpu is not None:
+            self._gpu.remove_endpoint(ep.index)
+        else:
+            self.index.remove_endpoint(ep.index)
 
 
 @register_plugin("inflight-load-producer",

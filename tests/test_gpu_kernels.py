@@ -67,10 +67,36 @@ class TestPrefixKernelsGPU:
         ext.table_update(keys, masks,
                          torch.from_numpy(h[:4].astype(np.uint64)).cuda(),
                          0, True)
-        cpu_idx2 = rc.PrefixIndex(100000)
-        # rebuild CPU side state equivalent: endpoint 0 without first 4
         gpu2 = ext.match_longest(keys, masks, hq, counts, 8).cpu().numpy()[0]
         assert gpu2[0] == 0  # leading blocks removed -> no prefix match
+        # the same history through the table model (ops.ref): equal
+        # (key, mask) entries, dead keys included, and equal matches for
+        # every endpoint, not endpoint 0 alone
+        from llm_d_inference_scheduler_amd.ops import ref
+        mk = torch.zeros(cap, dtype=torch.uint64)
+        mm = torch.zeros(cap, dtype=torch.uint64)
+        rng = np.random.default_rng(1)
+        rng.integers(0, 2**31 - 1, size=64 * 16)    # replay the draws above
+        for e in range(8):
+            n = int(rng.integers(1, len(h) + 1))
+            ref.table_update(mk, mm, torch.from_numpy(h[:n].astype(np.uint64)),
+                             e, False)
+        ref.table_update(mk, mm, torch.from_numpy(h[:4].astype(np.uint64)),
+                         0, True)
+
+        def entries(k, m):
+            k, m = k.cpu().numpy(), m.cpu().numpy()
+            return sorted(zip(k[k != 0].tolist(), m[k != 0].tolist()))
+        assert entries(keys, masks) == entries(mk, mm)
+        model2 = ref.match_longest(mk, mm, hq.cpu(), counts.cpu(), 8).numpy()[0]
+        assert list(gpu2) == list(model2)
+        assert list(gpu2[1:]) == list(gpu[1:])      # other endpoints unmoved
+        # and the host index agrees once endpoint 0 is rebuilt without its
+        # first four blocks
+        n0 = int(cpu[0])
+        cpu_idx.remove_endpoint(0)
+        cpu_idx.add(0, h[4:n0])
+        assert list(gpu2) == list(cpu_idx.match_longest(h, 8))
 
 
 class TestEngineKernelsGPU:
