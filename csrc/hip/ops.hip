@@ -50,6 +50,16 @@ hipError_t lds_paged_attention_split(const void*, const void*, const void*,
 hipError_t lds_sample(const void*, const float*, const int32_t*, const float*,
                       const int64_t*, const int32_t*, int, int, int, int64_t*,
                       float*, int32_t*, float*, hipStream_t);
+hipError_t lds_sample_ext(const void*, const float*, const int32_t*,
+                          const float*, const int64_t*, const int32_t*,
+                          const float*, const float*, const float*,
+                          const float*, const int32_t*, const int32_t*,
+                          int16_t*, int, int64_t, int, int, int, int, int64_t*,
+                          float*, int32_t*, float*, int64_t*, float*,
+                          hipStream_t);
+hipError_t lds_token_state_fill(int16_t*, int, int64_t, int, const int32_t*,
+                                int, const int32_t*, int64_t, const int64_t*,
+                                const int32_t*, hipStream_t);
 }
 
 namespace {
@@ -455,6 +465,126 @@ std::vector<torch::Tensor> sample(torch::Tensor logits,
   return {tokens, logprobs, n_kept, threshold};
 }
 
+// The token state of sample_ext / token_state_fill: int16 [R, Vs] on
+// `like`'s device, rows contiguous and 16-byte aligned, Vs = V rounded up
+// to a multiple of 8.
+void check_token_state(const torch::Tensor& state, const torch::Tensor& like,
+                       int64_t V) {
+  TORCH_CHECK(state.is_cuda() && state.device() == like.device(),
+              "state must be on the same device as the other arguments");
+  TORCH_CHECK(state.scalar_type() == at::kShort, "state must be int16");
+  TORCH_CHECK(state.dim() == 2, "state must be [R, Vs]");
+  TORCH_CHECK(state.is_contiguous(), "state must be contiguous");
+  TORCH_CHECK(state.size(1) == (V + 7) / 8 * 8, "state must have Vs = ",
+              (V + 7) / 8 * 8, " columns (V = ", V,
+              " rounded up to a multiple of 8), got ", state.size(1));
+  TORCH_CHECK(state.size(0) < (1LL << 31), "too many state rows");
+  TORCH_CHECK(((uintptr_t)state.data_ptr() & 15u) == 0,
+              "state must be 16-byte aligned");
+}
+
+// sample() plus repetition / presence / frequency penalties read from the
+// token state, min_p, the top-N raw logprobs and the state update. n_top is
+// the width of the top-N outputs; a row's top_n is clamped to it on device.
+// Rows of one launch must not share a state_row >= 0 (not checkable without
+// a sync; see DEVELOPMENT.md "Sampling").
+std::vector<torch::Tensor> sample_ext(
+    torch::Tensor logits, torch::Tensor temperature, torch::Tensor top_k,
+    torch::Tensor top_p, torch::Tensor seed, torch::Tensor pos,
+    torch::Tensor rep, torch::Tensor pres, torch::Tensor freq,
+    torch::Tensor min_p, torch::Tensor top_n, torch::Tensor state_row,
+    c10::optional<torch::Tensor> state, int64_t n_top) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be on GPU");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [B, V]");
+  TORCH_CHECK(logits.is_contiguous(), "logits must be contiguous");
+  const bool f32 = logits.scalar_type() == at::kFloat;
+  TORCH_CHECK(f32 || logits.scalar_type() == at::kBFloat16,
+              "logits must be bf16 or float32");
+  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) < (1LL << 31),
+              "vocabulary size out of range");
+  check_sample_param(temperature, logits, at::kFloat, "temperature");
+  check_sample_param(top_k, logits, at::kInt, "top_k");
+  check_sample_param(top_p, logits, at::kFloat, "top_p");
+  check_sample_param(seed, logits, at::kLong, "seed");
+  check_sample_param(pos, logits, at::kInt, "pos");
+  check_sample_param(rep, logits, at::kFloat, "rep");
+  check_sample_param(pres, logits, at::kFloat, "pres");
+  check_sample_param(freq, logits, at::kFloat, "freq");
+  check_sample_param(min_p, logits, at::kFloat, "min_p");
+  check_sample_param(top_n, logits, at::kInt, "top_n");
+  check_sample_param(state_row, logits, at::kInt, "state_row");
+  TORCH_CHECK(n_top >= 0 && n_top <= 20, "n_top must be in [0, 20], got ",
+              n_top);
+  int B = (int)logits.size(0), V = (int)logits.size(1);
+  int16_t* st = nullptr;
+  int R = 0;
+  int64_t Vs = 0;
+  if (state.has_value()) {
+    check_token_state(*state, logits, V);
+    st = state->data_ptr<int16_t>();
+    R = (int)state->size(0);
+    Vs = state->size(1);
+  }
+  auto opt = logits.options();
+  auto tokens = torch::empty({B}, opt.dtype(torch::kInt64));
+  auto logprobs = torch::empty({B}, opt.dtype(torch::kFloat32));
+  auto n_kept = torch::empty({B}, opt.dtype(torch::kInt32));
+  auto threshold = torch::empty({B}, opt.dtype(torch::kFloat32));
+  auto top_tokens = torch::empty({B, n_top}, opt.dtype(torch::kInt64));
+  auto top_logprobs = torch::empty({B, n_top}, opt.dtype(torch::kFloat32));
+  CHECK_HIP(lds_sample_ext(
+      logits.data_ptr(), temperature.data_ptr<float>(),
+      top_k.data_ptr<int32_t>(), top_p.data_ptr<float>(),
+      seed.data_ptr<int64_t>(), pos.data_ptr<int32_t>(),
+      rep.data_ptr<float>(), pres.data_ptr<float>(), freq.data_ptr<float>(),
+      min_p.data_ptr<float>(), top_n.data_ptr<int32_t>(),
+      state_row.data_ptr<int32_t>(), st, R, Vs, B, V, f32 ? 1 : 0,
+      (int)n_top, tokens.data_ptr<int64_t>(), logprobs.data_ptr<float>(),
+      n_kept.data_ptr<int32_t>(), threshold.data_ptr<float>(),
+      top_tokens.data_ptr<int64_t>(), top_logprobs.data_ptr<float>(),
+      cur_stream()));
+  return {tokens, logprobs, n_kept, threshold, top_tokens, top_logprobs};
+}
+
+// Rebuild the listed state rows from token histories: for entry q, row
+// rows[q] is cleared, tokens[offsets[q] : offsets[q] + n_prompt[q]] set the
+// prompt bit and tokens[offsets[q] + n_prompt[q] : offsets[q + 1]] are
+// counted. V is the vocabulary size (state has Vs columns). The kernel
+// clamps offsets into tokens and skips rows and ids out of range.
+void token_state_fill(torch::Tensor state, torch::Tensor rows,
+                      torch::Tensor tokens, torch::Tensor offsets,
+                      torch::Tensor n_prompt, int64_t V) {
+  TORCH_CHECK(V >= 1 && V < (1LL << 31), "vocabulary size out of range");
+  TORCH_CHECK(rows.is_cuda(), "rows must be on GPU");
+  check_token_state(state, rows, V);
+  for (const torch::Tensor* t : {&tokens, &offsets, &n_prompt})
+    TORCH_CHECK(t->is_cuda() && t->device() == rows.device(),
+                "rows, tokens, offsets and n_prompt must be on one device");
+  TORCH_CHECK(rows.scalar_type() == at::kInt &&
+              tokens.scalar_type() == at::kInt &&
+              n_prompt.scalar_type() == at::kInt,
+              "rows, tokens and n_prompt must be int32");
+  TORCH_CHECK(offsets.scalar_type() == at::kLong, "offsets must be int64");
+  TORCH_CHECK(rows.dim() == 1 && tokens.dim() == 1 && offsets.dim() == 1 &&
+              n_prompt.dim() == 1, "rows, tokens, offsets and n_prompt "
+              "must be one-dimensional");
+  TORCH_CHECK(rows.is_contiguous() && tokens.is_contiguous() &&
+              offsets.is_contiguous() && n_prompt.is_contiguous(),
+              "rows, tokens, offsets and n_prompt must be contiguous");
+  TORCH_CHECK(n_prompt.numel() == rows.numel() &&
+              offsets.numel() == rows.numel() + 1,
+              "n_prompt must hold one value per row and offsets one more, "
+              "got ", rows.numel(), " rows, ", n_prompt.numel(),
+              " n_prompt, ", offsets.numel(), " offsets");
+  TORCH_CHECK(rows.numel() < (1LL << 31), "too many rows");
+  CHECK_HIP(lds_token_state_fill(
+      state.data_ptr<int16_t>(), (int)state.size(0), state.size(1), (int)V,
+      rows.data_ptr<int32_t>(), (int)rows.numel(),
+      tokens.data_ptr<int32_t>(), tokens.numel(),
+      offsets.data_ptr<int64_t>(), n_prompt.data_ptr<int32_t>(),
+      cur_stream()));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -504,4 +634,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(tokens, logprobs, n_kept, threshold)",
         py::arg("logits"), py::arg("temperature"), py::arg("top_k"),
         py::arg("top_p"), py::arg("seed"), py::arg("pos"));
+  m.def("sample_ext", &sample_ext,
+        "sample with penalties from the token state, min_p and top-N -> "
+        "(tokens, logprobs, n_kept, threshold, top_tokens, top_logprobs)",
+        py::arg("logits"), py::arg("temperature"), py::arg("top_k"),
+        py::arg("top_p"), py::arg("seed"), py::arg("pos"), py::arg("rep"),
+        py::arg("pres"), py::arg("freq"), py::arg("min_p"),
+        py::arg("top_n"), py::arg("state_row"),
+        py::arg("state") = py::none(), py::arg("n_top") = 0);
+  m.def("token_state_fill", &token_state_fill,
+        "rebuild token-state rows from prompt and output token lists",
+        py::arg("state"), py::arg("rows"), py::arg("tokens"),
+        py::arg("offsets"), py::arg("n_prompt"), py::arg("V"));
 }

@@ -18,6 +18,14 @@
 // Masses are accumulated as 2^-32 fixed point in 64-bit LDS atomics:
 // integer adds commute, so a row's result does not depend on the order in
 // which waves reach the histogram (nor on batch position or batch size).
+//
+// sample_ext is the same kernel with EXT = true: every pass sees the
+// penalised fp32 logit x (repetition, frequency and presence penalties from
+// the request's token-state row, computed on the fly), the selects run on
+// the fp32 key of x (4 digit passes, also for bf16 input), min_p joins the
+// thresholds, a top-N phase on the raw keys reports the alternatives, and
+// the chosen token is counted into the state row. token_state_fill builds a
+// state row from a request's prompt and output so far.
 #include "hip_common.h"
 
 #include <cfloat>
@@ -88,6 +96,111 @@ __device__ __forceinline__ void for_row(const T* __restrict__ row, int V,
   const int t = head + nvec * VEC + tid;
   if (t < V) f(t, row[t]);
 }
+
+// for_row with the request's token-state row alongside (sample_ext): calls
+// f(index, raw element, state element). The logits keep for_row's thread
+// mapping and order, so sums over a row round as they do there. A state row
+// starts 16-byte aligned (Vs % 8 == 0), so when the logits row does too
+// (head == 0) the state is read with one vector load per logits vector;
+// otherwise element by element. st == nullptr (no state) passes 0.
+template <typename T> struct StateVec;
+template <> struct StateVec<short> { typedef short8 type; };
+template <> struct StateVec<float> { typedef short4v type; };
+
+template <typename T, typename F>
+__device__ __forceinline__ void for_row_state(const T* __restrict__ row,
+                                              const short* st, int V, F&& f) {
+  typedef typename RowVec<T>::type vec_t;
+  typedef typename StateVec<T>::type svec_t;
+  constexpr int VEC = 16 / (int)sizeof(T);
+  const int tid = threadIdx.x;
+  int head = (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) /
+                   sizeof(T));
+  if (head > V) head = V;
+  if (tid < head) f(tid, row[tid], st ? st[tid] : (short)0);
+  const int nvec = (V - head) / VEC;
+  const vec_t* rv = (const vec_t*)(row + head);
+  for (int c = tid; c < nvec; c += SAMPLER_THREADS) {
+    const vec_t v = rv[c];
+    const int base = head + c * VEC;
+    svec_t sv = (svec_t)(short)0;
+    if (st) {
+      if (head == 0) {
+        sv = ((const svec_t*)st)[c];
+      } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) sv[j] = st[base + j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) f(base + j, (T)v[j], (short)sv[j]);
+  }
+  const int t = head + nvec * VEC + tid;
+  if (t < V) f(t, row[t], st ? st[t] : (short)0);
+}
+
+// Element access of sample_kernel<T, EXT>. Without EXT it is the identity:
+// the value is the raw logit, the radix key is the key of its storage type
+// and no state is read. With EXT the value is the penalised fp32 logit x of
+// step 0 of the contract, computed on the fly from the raw logit and the
+// state element, each operation rounded on its own (no FMA contraction),
+// and the radix key is the fp32 key of x.
+constexpr int STATE_COUNT_MASK = 0x3FFF;       // c, saturating at 16383
+
+template <typename T, bool EXT> struct Elem;
+template <typename T> struct Elem<T, false> {
+  typedef T key_t;
+  __device__ __forceinline__ float x(T raw, short) const {
+    return raw_to_f32(raw);
+  }
+  __device__ __forceinline__ uint32_t key(T raw, short) const {
+    return key_of(raw);
+  }
+  template <typename F>
+  __device__ __forceinline__ void each(const T* __restrict__ row, int V,
+                                       F&& f) const {
+    for_row(row, V, [&](int i, T raw) { f(i, raw, (short)0); });
+  }
+};
+template <typename T> struct Elem<T, true> {
+  typedef float key_t;
+  const short* st;
+  float rep, pres, freq;
+  __device__ __forceinline__ float x(T raw, short s) const {
+    float v = raw_to_f32(raw);
+    if (s != 0) v = v > 0.f ? __fdiv_rn(v, rep) : __fmul_rn(v, rep);
+    const int c = (int)s & STATE_COUNT_MASK;
+    v = __fsub_rn(v, __fmul_rn(freq, (float)c));
+    return __fsub_rn(v, c > 0 ? pres : 0.f);
+  }
+  __device__ __forceinline__ uint32_t key(T raw, short s) const {
+    return key_of(x(raw, s));
+  }
+  template <typename F>
+  __device__ __forceinline__ void each(const T* __restrict__ row, int V,
+                                       F&& f) const {
+    for_row_state(row, st, V, f);
+  }
+};
+
+// What sample_ext adds to the launch; the plain sampler carries nothing.
+struct ExtArgs {
+  const float* rep;
+  const float* pres;
+  const float* freq;
+  const float* min_p;
+  const int32_t* top_n;
+  const int32_t* state_row;
+  short* state;              // [R, Vs] int16, or null: no row has state
+  int64_t Vs;
+  int R;
+  int n_top;                 // width of the top-N outputs, 0..TOPN_MAX
+  int64_t* top_tokens;       // [B, n_top]
+  float* top_logprobs;       // [B, n_top]
+};
+struct NoExtArgs {};
+template <bool EXT> struct ExtArgsOf { typedef NoExtArgs type; };
+template <> struct ExtArgsOf<true> { typedef ExtArgs type; };
 
 // ---- workgroup reductions (every thread calls; result to all threads) ----
 
@@ -237,15 +350,129 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1,
   o0 = c0; o1 = c1; o2 = c2; o3 = c3;
 }
 
+// ---- top-N alternatives (sample_ext) ----
+constexpr int TOPN_MAX = 20;
+
+// Key of a raw logit for top-N: key_of with -0 folded onto +0, so that
+// "equal value" and "equal key" are the same thing.
+__device__ __forceinline__ uint32_t topn_key(short v) {
+  return key_of(v == (short)0x8000 ? (short)0 : v);
+}
+__device__ __forceinline__ uint32_t topn_key(float v) {
+  return key_of(v + 0.f);
+}
+
+// The N entries of one row with the largest raw logit, ordered by (value
+// descending, index ascending), as (index, logit - lse); entries from N to
+// n_top are (-1, -inf). Every thread of the block calls.
+//   1. count select with k = N on the raw keys: the threshold key, and how
+//      many of the elements that carry it are still needed (k_rem);
+//   2. when not all of them are needed, a second count select, on V-1-index
+//      among the elements with the threshold key: the k_rem-th lowest index;
+//   3. one collect pass into LDS (exactly N entries), then each entry finds
+//      its rank among the N by counting.
+// bf16 rows tie heavily, so step 2 is a common path there.
 template <typename T>
+__device__ __forceinline__ void topn_phase(const T* __restrict__ row, int V,
+                                           int N, int n_top, float lse,
+                                           Hist& h,
+                                           int64_t* __restrict__ out_tok,
+                                           float* __restrict__ out_lp) {
+  constexpr int KEYBITS = 8 * (int)sizeof(T);
+  constexpr int NDIG = (int)sizeof(T);
+  __shared__ uint32_t s_key[TOPN_MAX];
+  __shared__ int s_idx[TOPN_MAX];
+  __shared__ int s_n;
+  const int tid = threadIdx.x;
+  if (N > n_top) N = n_top;
+  if (N > V) N = V;
+  if (N < 0) N = 0;
+  if (tid >= N && tid < n_top) {
+    out_tok[tid] = -1;
+    out_lp[tid] = -INFINITY;
+  }
+  if (N == 0) return;
+
+  uint32_t prefix = 0;
+  int k_rem = N, ties = 0;
+  for (int d = 0; d < NDIG; ++d) {
+    const int shift = KEYBITS - 8 * (d + 1);
+    hist_clear(h);
+    for_row(row, V, [&](int, T raw) {
+      const uint32_t key = topn_key(raw);
+      if ((uint32_t)((uint64_t)key >> (shift + 8)) == prefix)
+        atomicAdd(&h.cnt[(key >> shift) & 0xFFu], 1);
+    });
+    int above;
+    const int b = select_by_count(h, k_rem, above);
+    k_rem -= above;
+    prefix = (prefix << 8) | (uint32_t)b;
+    ties = h.cnt[b];
+    __syncthreads();                     // read before the next clear
+  }
+
+  // elements with the threshold key are taken up to this index
+  int idx_max = V - 1;
+  if (k_rem < ties) {
+    const int nbits = 32 - __clz(V - 1);           // ties >= 2, so V >= 2
+    const int nd = (nbits + 7) / 8;
+    uint32_t ip = 0;
+    int kr = k_rem;
+    for (int d = 0; d < nd; ++d) {
+      const int shift = 8 * (nd - 1 - d);
+      hist_clear(h);
+      for_row(row, V, [&](int i, T raw) {
+        if (topn_key(raw) != prefix) return;
+        const uint32_t ik = (uint32_t)(V - 1 - i);
+        if ((uint32_t)((uint64_t)ik >> (shift + 8)) == ip)
+          atomicAdd(&h.cnt[(ik >> shift) & 0xFFu], 1);
+      });
+      int above;
+      const int b = select_by_count(h, kr, above);
+      kr -= above;
+      ip = (ip << 8) | (uint32_t)b;
+    }
+    idx_max = V - 1 - (int)ip;
+  }
+
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  for_row(row, V, [&](int i, T raw) {
+    const uint32_t key = topn_key(raw);
+    if (key > prefix || (key == prefix && i <= idx_max)) {
+      const int j = atomicAdd(&s_n, 1);
+      if (j < TOPN_MAX) { s_key[j] = key; s_idx[j] = i; }
+    }
+  });
+  __syncthreads();
+  const int n = s_n < N ? s_n : N;
+  if (tid < n) {
+    const uint32_t key = s_key[tid];
+    const int idx = s_idx[tid];
+    int rank = 0;
+    for (int j = 0; j < n; ++j)
+      rank += (s_key[j] > key || (s_key[j] == key && s_idx[j] < idx)) ? 1 : 0;
+    out_tok[rank] = idx;
+    out_lp[rank] = key_to_f32<T>(key) - lse;
+  }
+  __syncthreads();
+}
+
+// sample_kernel<T, false> is the plain sampler (lds_sample); <T, true> is
+// sample_ext: penalties from the token state, min_p, top-N alternatives and
+// the state update, sharing every pass with the plain one through Elem.
+template <typename T, bool EXT>
 __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
     const T* __restrict__ logits, const float* __restrict__ temperature,
     const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
     const int64_t* __restrict__ seed, const int32_t* __restrict__ pos, int V,
     int64_t* __restrict__ tokens, float* __restrict__ logprobs,
-    int32_t* __restrict__ n_kept, float* __restrict__ threshold) {
-  constexpr int KEYBITS = 8 * (int)sizeof(T);
-  constexpr int NDIG = (int)sizeof(T);
+    int32_t* __restrict__ n_kept, float* __restrict__ threshold,
+    typename ExtArgsOf<EXT>::type ea) {
+  typedef Elem<T, EXT> elem_t;
+  typedef typename elem_t::key_t K;
+  constexpr int KEYBITS = 8 * (int)sizeof(K);
+  constexpr int NDIG = (int)sizeof(K);
   __shared__ Hist h;
   __shared__ float red_f[SAMPLER_WAVES];
   __shared__ int red_i[SAMPLER_WAVES];
@@ -254,10 +481,25 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
   const int tid = threadIdx.x;
   const T* row = logits + (int64_t)r * V;
 
-  // ---- pass 1: raw max (lowest index), online sum of exp(l - max) ----
+  elem_t el;
+  short* st_w = nullptr;                 // this row's state, if it has one
+  if constexpr (EXT) {
+    const int sr = ea.state_row[r];
+    if (ea.state != nullptr && sr >= 0 && sr < ea.R)
+      st_w = ea.state + (int64_t)sr * ea.Vs;
+    el.st = st_w;
+    el.rep = ea.rep[r];
+    el.pres = ea.pres[r];
+    el.freq = ea.freq[r];
+  }
+
+  // ---- pass 1: raw max (lowest index), online sum of exp(l - max); with
+  // EXT also the maximum of x, which takes over argmax and m ----
   float m_t = -FLT_MAX, s_t = 0.f;
   int i_t = 0x7FFFFFFF;
-  for_row(row, V, [&](int i, T raw) {
+  float mx_t = -FLT_MAX;
+  int ix_t = 0x7FFFFFFF;
+  el.each(row, V, [&](int i, T raw, short s) {
     const float l = raw_to_f32(raw);
     if (l > m_t) {
       s_t = s_t * expf(m_t - l) + 1.f;
@@ -267,30 +509,54 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
       s_t += expf(l - m_t);
       if (l == m_t && i < i_t) i_t = i;
     }
+    if constexpr (EXT) argmax_merge(mx_t, ix_t, el.x(raw, s), i);
   });
   float M = m_t;
   int arg = i_t;
   block_argmax(M, arg, red_f, red_i);
+  float Mx = M;                          // maximum of x: the raw one or
+  if constexpr (EXT) {                   // the penalised one
+    Mx = mx_t;
+    arg = ix_t;
+    block_argmax(Mx, arg, red_f, red_i);
+  }
   if ((uint32_t)arg >= (uint32_t)V) arg = 0;     // an all-NaN row
   const float S = block_sum_f32(s_t * expf(m_t - M), red_f);
   const float lse = M + logf(S);
+
+  if constexpr (EXT) {
+    if (ea.n_top > 0)
+      topn_phase<T>(row, V, ea.top_n[r], ea.n_top, lse, h,
+                    ea.top_tokens + (int64_t)r * ea.n_top,
+                    ea.top_logprobs + (int64_t)r * ea.n_top);
+  }
 
   const float T_ = temperature[r];
   if (!(T_ > 0.f)) {
     if (tid == 0) {
       tokens[r] = arg;
-      logprobs[r] = M - lse;
+      if constexpr (EXT) {
+        logprobs[r] = raw_to_f32(row[arg]) - lse;
+        // every read of the state row lies before block_argmax's barrier
+        if (st_w != nullptr) {
+          const short s = st_w[arg];
+          if (((int)s & STATE_COUNT_MASK) < STATE_COUNT_MASK)
+            st_w[arg] = (short)(s + 1);
+        }
+      } else {
+        logprobs[r] = M - lse;
+      }
       n_kept[r] = V;
       threshold[r] = -INFINITY;
     }
     return;
   }
   const float inv = 1.0f / T_;
-  const float mz = __fmul_rn(M, inv);
+  const float mz = __fmul_rn(Mx, inv);
   const int k = top_k[r];
   const float p = top_p[r];
 
-  // ---- top-k: the k-th largest raw key, one digit per pass ----
+  // ---- top-k: the k-th largest key, one digit per pass ----
   float tau = -INFINITY;
   if (k > 0 && k < V) {
     uint32_t prefix = 0;
@@ -298,8 +564,8 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
     for (int d = 0; d < NDIG; ++d) {
       const int shift = KEYBITS - 8 * (d + 1);
       hist_clear(h);
-      for_row(row, V, [&](int, T raw) {
-        const uint32_t key = key_of(raw);
+      el.each(row, V, [&](int, T raw, short s) {
+        const uint32_t key = el.key(raw, s);
         if ((uint32_t)((uint64_t)key >> (shift + 8)) == prefix)
           atomicAdd(&h.cnt[(key >> shift) & 0xFFu], 1);
       });
@@ -308,7 +574,7 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
       k_rem -= above;
       prefix = (prefix << 8) | (uint32_t)b;
     }
-    tau = __fmul_rn(key_to_f32<T>(prefix), inv);
+    tau = __fmul_rn(key_to_f32<K>(prefix), inv);
   }
 
   // ---- top-p over {z >= tau}: largest v with mass{z >= v} >= p * W ----
@@ -319,10 +585,10 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
     for (int d = 0; d < NDIG; ++d) {
       const int shift = KEYBITS - 8 * (d + 1);
       hist_clear(h);
-      for_row(row, V, [&](int, T raw) {
-        const uint32_t key = key_of(raw);
+      el.each(row, V, [&](int, T raw, short s) {
+        const uint32_t key = el.key(raw, s);
         if ((uint32_t)((uint64_t)key >> (shift + 8)) != prefix) return;
-        const float z = __fmul_rn(raw_to_f32(raw), inv);
+        const float z = __fmul_rn(el.x(raw, s), inv);
         if (!(z >= tau)) return;
         const float w = expf(__fsub_rn(z, mz));
         const int bin = (key >> shift) & 0xFFu;
@@ -341,7 +607,14 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
       const int b = select_by_mass(h, target, above);
       prefix = (prefix << 8) | (uint32_t)b;
     }
-    tau = fmaxf(tau, __fmul_rn(key_to_f32<T>(prefix), inv));
+    tau = fmaxf(tau, __fmul_rn(key_to_f32<K>(prefix), inv));
+  }
+
+  // ---- min_p: tau_m = max z + log(min_p), the log correctly rounded ----
+  if constexpr (EXT) {
+    const float mp = ea.min_p[r];
+    if (mp > 0.f)
+      tau = fmaxf(tau, __fadd_rn(mz, (float)log((double)mp)));
   }
 
   // ---- Gumbel-max over the kept set ----
@@ -353,8 +626,8 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
   int kept = 0;
   int cached = -1;
   uint32_t x0 = 0, x1 = 0, x2 = 0, x3 = 0;
-  for_row(row, V, [&](int i, T raw) {
-    const float z = __fmul_rn(raw_to_f32(raw), inv);
+  el.each(row, V, [&](int i, T raw, short s) {
+    const float z = __fmul_rn(el.x(raw, s), inv);
     if (!(z >= tau)) return;
     ++kept;
     const int blk = i >> 2;
@@ -378,6 +651,95 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_kernel(
     logprobs[r] = raw_to_f32(row[best_i]) - lse;
     n_kept[r] = kept;
     threshold[r] = __fmul_rn(tau, T_);
+    if constexpr (EXT) {
+      // the draw's barriers lie behind every read of the state row, and
+      // this workgroup is the row's only writer
+      if (st_w != nullptr) {
+        const short s = st_w[best_i];
+        if (((int)s & STATE_COUNT_MASK) < STATE_COUNT_MASK)
+          st_w[best_i] = (short)(s + 1);
+      }
+    }
+  }
+}
+
+// ---- token_state_fill ----
+// One workgroup per listed state row: clear columns [0, V), set bit 14 for
+// the prompt ids, count the output ids. Two ids 2j and 2j+1 share a 32-bit
+// word (Vs is even, so a word never spans two rows), and the same id can
+// come hundreds of times in one call, so all updates are 32-bit atomics on
+// the word: an OR for bit 14, and for the count a compare-and-swap loop
+// that adds to the 14-bit field alone and stops at 16383, so that nothing
+// ever carries into bit 14 or into the neighbouring half-word. Equal ids
+// within a wave are added in one go by the lowest lane that holds them,
+// which keeps a 16400-fold id at a few hundred swaps.
+constexpr int FILL_THREADS = 1024;
+
+__global__ __launch_bounds__(FILL_THREADS) void token_state_fill_kernel(
+    short* __restrict__ state, int R, int64_t Vs, int V,
+    const int32_t* __restrict__ rows, const int32_t* __restrict__ toks,
+    int64_t n_toks, const int64_t* __restrict__ offsets,
+    const int32_t* __restrict__ n_prompt) {
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int sr = rows[q];
+  if (sr < 0 || sr >= R) return;
+  short* st = state + (int64_t)sr * Vs;
+
+  // clear [0, V): whole 16-byte vectors, then the last V % 8 elements one
+  // by one (padding columns are never written)
+  const int nvec = V / 8;
+  short8* sv = (short8*)st;
+  for (int c = tid; c < nvec; c += FILL_THREADS) sv[c] = (short8)(short)0;
+  if (nvec * 8 + tid < V) st[nvec * 8 + tid] = 0;
+  __threadfence_block();
+  __syncthreads();
+
+  int64_t beg = offsets[q], end = offsets[q + 1];
+  beg = beg < 0 ? 0 : (beg > n_toks ? n_toks : beg);
+  end = end < beg ? beg : (end > n_toks ? n_toks : end);
+  int64_t np = n_prompt[q];
+  np = np < 0 ? 0 : (np > end - beg ? end - beg : np);
+  uint32_t* words = (uint32_t*)st;
+
+  for (int64_t t = beg + tid; t < beg + np; t += FILL_THREADS) {
+    const int id = toks[t];
+    if (id < 0 || id >= V) continue;
+    atomicOr(&words[id >> 1], 0x4000u << ((id & 1) * 16));
+  }
+
+  // every lane of a wave takes part in each round of the loop below
+  const int64_t n_out = end - (beg + np);
+  const int64_t rounds = (n_out + FILL_THREADS - 1) / FILL_THREADS;
+  for (int64_t it = 0; it < rounds; ++it) {
+    const int64_t t = beg + np + it * FILL_THREADS + tid;
+    int id = t < end ? toks[t] : -1;
+    if (id >= V) id = -1;
+    bool todo = id >= 0;
+    while (true) {
+      const unsigned long long live = __ballot(todo);
+      if (live == 0) break;
+      const int leader = __ffsll((long long)live) - 1;
+      const int lid = __shfl(id, leader, WAVE);
+      const bool mine = todo && id == lid;
+      const int add = __popcll(__ballot(mine));
+      if (tid % WAVE == leader) {
+        const int shift = (lid & 1) * 16;
+        uint32_t* w = &words[lid >> 1];
+        uint32_t old = *w;
+        while (true) {
+          const int c = (int)((old >> shift) & (uint32_t)STATE_COUNT_MASK);
+          if (c == STATE_COUNT_MASK) break;
+          int nc = c + add;
+          if (nc > STATE_COUNT_MASK) nc = STATE_COUNT_MASK;
+          const uint32_t want = old + ((uint32_t)(nc - c) << shift);
+          const uint32_t prev = atomicCAS(w, old, want);
+          if (prev == old) break;
+          old = prev;
+        }
+      }
+      if (mine) todo = false;
+    }
   }
 }
 
@@ -396,14 +758,66 @@ hipError_t lds_sample(const void* logits, const float* temperature,
   if (V <= 0) return hipErrorInvalidValue;
   dim3 grid((uint32_t)B), block(SAMPLER_THREADS);
   if (is_f32) {
-    hipLaunchKernelGGL(sample_kernel<float>, grid, block, 0, stream,
+    hipLaunchKernelGGL((sample_kernel<float, false>), grid, block, 0, stream,
                        (const float*)logits, temperature, top_k, top_p, seed,
-                       pos, V, tokens, logprobs, n_kept, threshold);
+                       pos, V, tokens, logprobs, n_kept, threshold,
+                       NoExtArgs{});
   } else {
-    hipLaunchKernelGGL(sample_kernel<short>, grid, block, 0, stream,
+    hipLaunchKernelGGL((sample_kernel<short, false>), grid, block, 0, stream,
                        (const short*)logits, temperature, top_k, top_p, seed,
-                       pos, V, tokens, logprobs, n_kept, threshold);
+                       pos, V, tokens, logprobs, n_kept, threshold,
+                       NoExtArgs{});
   }
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+// sample with penalties, min_p, top-N and the token-state update
+// (DEVELOPMENT.md "Sampling"). state: [R, Vs] int16 or null; Vs % 8 == 0,
+// Vs >= V and the base 16-byte aligned (the binding checks). top_tokens /
+// top_logprobs: [B, n_top], n_top in [0, 20].
+hipError_t lds_sample_ext(const void* logits, const float* temperature,
+                          const int32_t* top_k, const float* top_p,
+                          const int64_t* seed, const int32_t* pos,
+                          const float* rep, const float* pres,
+                          const float* freq, const float* min_p,
+                          const int32_t* top_n, const int32_t* state_row,
+                          int16_t* state, int R, int64_t Vs, int B, int V,
+                          int is_f32, int n_top, int64_t* tokens,
+                          float* logprobs, int32_t* n_kept, float* threshold,
+                          int64_t* top_tokens, float* top_logprobs,
+                          hipStream_t stream) {
+  if (B == 0) return hipSuccess;
+  if (V <= 0 || n_top < 0 || n_top > TOPN_MAX) return hipErrorInvalidValue;
+  if (state != nullptr && (Vs < V || Vs % 8 != 0 || R < 0))
+    return hipErrorInvalidValue;
+  ExtArgs ea{rep, pres, freq, min_p, top_n, state_row, (short*)state, Vs, R,
+             n_top, top_tokens, top_logprobs};
+  dim3 grid((uint32_t)B), block(SAMPLER_THREADS);
+  if (is_f32) {
+    hipLaunchKernelGGL((sample_kernel<float, true>), grid, block, 0, stream,
+                       (const float*)logits, temperature, top_k, top_p, seed,
+                       pos, V, tokens, logprobs, n_kept, threshold, ea);
+  } else {
+    hipLaunchKernelGGL((sample_kernel<short, true>), grid, block, 0, stream,
+                       (const short*)logits, temperature, top_k, top_p, seed,
+                       pos, V, tokens, logprobs, n_kept, threshold, ea);
+  }
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+// state: [R, Vs] int16; rows, n_prompt: [n]; offsets: [n + 1] into toks.
+hipError_t lds_token_state_fill(int16_t* state, int R, int64_t Vs, int V,
+                                const int32_t* rows, int n,
+                                const int32_t* toks, int64_t n_toks,
+                                const int64_t* offsets,
+                                const int32_t* n_prompt, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (V <= 0 || Vs < V || Vs % 8 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(token_state_fill_kernel, dim3((uint32_t)n),
+                     dim3(FILL_THREADS), 0, stream, (short*)state, R, Vs, V,
+                     rows, toks, n_toks, offsets, n_prompt);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -51,6 +51,13 @@ class EngineRequest:
     top_p: float = 1.0              # 1.0 = off
     seed: Optional[int] = None      # None = derived from the worker's seed
     logprobs: bool = False          # return the sampled tokens' logprobs
+    # ops.sample_ext fields; any of them set routes the request's steps
+    # through it instead
+    repetition_penalty: float = 1.0     # 1.0 = off
+    presence_penalty: float = 0.0       # 0 = off
+    frequency_penalty: float = 0.0      # 0 = off
+    min_p: float = 0.0                  # 0 = off
+    top_logprobs: int = 0               # alternatives per token, 0..20
     # runtime state
     computed: int = 0               # prompt tokens already prefilled
     generated: List[int] = field(default_factory=list)
@@ -63,6 +70,11 @@ class EngineRequest:
     _prompt_np: Optional[object] = field(default=None, repr=False)
     logprob_vals: List[float] = field(default_factory=list)
     _seed64: Optional[int] = field(default=None, repr=False)  # resolved u64
+    # per generated token: [(token id, logprob)] * top_logprobs
+    top_logprob_vals: List[list] = field(default_factory=list)
+    # prompt length at admission: _preempt folds the generation into
+    # prompt_tokens, the token state must still count it as output
+    orig_prompt_len: Optional[int] = None
 
     def __post_init__(self):
         if not self.arrival_t:
@@ -82,7 +94,20 @@ class EngineRequest:
         """True when the request sets a field only the fused sampler
         implements."""
         return (self.top_k > 0 or self.top_p < 1.0 or self.seed is not None
-                or self.logprobs)
+                or self.logprobs or self.uses_ext)
+
+    @property
+    def needs_token_state(self) -> bool:
+        """True when a penalty is on: the request needs a token-state row."""
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+                or self.frequency_penalty != 0.0)
+
+    @property
+    def uses_ext(self) -> bool:
+        """True when the request sets a field only ops.sample_ext
+        implements."""
+        return (self.needs_token_state or self.min_p > 0.0
+                or self.top_logprobs > 0)
 
 
 @dataclass
@@ -103,6 +128,10 @@ class RequestOutput:
     # whole generation's on finish
     new_logprobs: Optional[List[float]] = None
     all_logprobs: Optional[List[float]] = None
+    # top_logprobs > 0 requests: per token, the [(token id, logprob)] of the
+    # best raw logits, best first
+    new_top_logprobs: Optional[List[list]] = None
+    all_top_logprobs: Optional[List[list]] = None
     # usage on finish:
     prompt_tokens: int = 0
     completion_tokens: int = 0
@@ -149,6 +178,16 @@ class DecodeState:
         self.top_p = None
         self.seed = None
         self.pos_off = None
+        # ops.sample_ext parameters per row. They hold their off values
+        # except on the rows in ext_rows, which join() resets when such a
+        # row goes to a request that does not use them.
+        self.rep = None
+        self.pres = None
+        self.freq = None
+        self.min_p = None
+        self.top_n = None
+        self.state_row = None
+        self.ext_rows: set = set()
         self.free_rows: List[int] = []
         self.row_of: Dict[str, int] = {}
         self._active_ids: List[str] = []
@@ -166,6 +205,18 @@ class DecodeState:
         pp = torch.ones(new_cap, dtype=torch.float32, device=self.device)
         sd = torch.zeros(new_cap, dtype=torch.int64, device=self.device)
         po = torch.zeros(new_cap, dtype=torch.int32, device=self.device)
+        f32, i32 = torch.float32, torch.int32
+        ext = {"rep": torch.ones(new_cap, dtype=f32, device=self.device),
+               "pres": torch.zeros(new_cap, dtype=f32, device=self.device),
+               "freq": torch.zeros(new_cap, dtype=f32, device=self.device),
+               "min_p": torch.zeros(new_cap, dtype=f32, device=self.device),
+               "top_n": torch.zeros(new_cap, dtype=i32, device=self.device),
+               "state_row": torch.full((new_cap,), -1, dtype=i32,
+                                       device=self.device)}
+        for name, t in ext.items():
+            if old:
+                t[:old] = getattr(self, name)
+            setattr(self, name, t)
         if old:
             bt[:old] = self.bt
             sl[:old] = self.seq_lens
@@ -186,8 +237,25 @@ class DecodeState:
         return self.free_rows.pop()
 
     def join(self, req: EngineRequest, table: List[int], seq_len: int,
-             last_token: int) -> None:
+             last_token: int, state_row: int = -1) -> None:
+        """state_row: the request's row of the token-state pool, -1 = none."""
         row = self.take_row()
+        if req.uses_ext:
+            self.rep[row] = req.repetition_penalty
+            self.pres[row] = req.presence_penalty
+            self.freq[row] = req.frequency_penalty
+            self.min_p[row] = req.min_p
+            self.top_n[row] = req.top_logprobs
+            self.state_row[row] = state_row
+            self.ext_rows.add(row)
+        elif row in self.ext_rows:
+            self.rep[row] = 1.0
+            self.pres[row] = 0.0
+            self.freq[row] = 0.0
+            self.min_p[row] = 0.0
+            self.top_n[row] = 0
+            self.state_row[row] = -1
+            self.ext_rows.discard(row)
         self.row_of[req.request_id] = row
         # any membership mutation invalidates the cached row-index tensor:
         # an identical id list can recur with different row assignments
@@ -225,6 +293,70 @@ class DecodeState:
                 device=self.device)
             self._active_ids = list(ids)
         return self._rows_t
+
+
+class TokenStatePool:
+    """Token-occurrence state of the penalised requests (DEVELOPMENT.md
+    "Sampling"): one int16 row of Vs columns per request, keyed by request
+    id, on the device. Allocated at the first request that needs it and
+    doubled on demand; the sampler itself counts each chosen token, so a
+    decode step moves nothing from the host."""
+
+    def __init__(self, vocab_size: int, device: torch.device):
+        self.V = vocab_size
+        self.device = device
+        self.tensor: Optional[torch.Tensor] = None
+        self.free_rows: List[int] = []
+        self.row_of: Dict[str, int] = {}
+
+    def take(self, request_id: str) -> int:
+        row = self.row_of.get(request_id)
+        if row is not None:
+            return row
+        if not self.free_rows:
+            old = 0 if self.tensor is None else self.tensor.shape[0]
+            new = max(4, old * 2)
+            if old and self.device.type == "cuda":
+                # rows may be in use by work queued on another stream
+                torch.cuda.synchronize(self.device)
+            t = ops.token_state_alloc(new, self.V, self.device)
+            if old:
+                t[:old] = self.tensor
+            self.tensor = t
+            self.free_rows.extend(range(new - 1, old - 1, -1))
+        row = self.free_rows.pop()
+        self.row_of[request_id] = row
+        return row
+
+    def free(self, request_id: str) -> None:
+        row = self.row_of.pop(request_id, None)
+        if row is not None:
+            self.free_rows.append(row)
+
+    def fill(self, reqs: List[EngineRequest]) -> None:
+        """Take a row for each request that needs one and rebuild it from
+        the original prompt and the output so far."""
+        reqs = [r for r in reqs if r.needs_token_state]
+        if not reqs:
+            return
+        rows = [self.take(r.request_id) for r in reqs]
+        toks: List[int] = []
+        offs, n_p = [0], []
+        for r in reqs:
+            n = r.prompt_len if r.orig_prompt_len is None \
+                else r.orig_prompt_len
+            toks.extend(r.prompt_tokens[:n])
+            toks.extend(r.generated)
+            offs.append(len(toks))
+            n_p.append(n)
+        dev = self.device
+        ops.token_state_fill(
+            self.tensor,
+            torch.tensor(rows, dtype=torch.int32).to(dev, non_blocking=True),
+            torch.tensor(toks, dtype=torch.int32).to(dev, non_blocking=True),
+            torch.tensor(offs, dtype=torch.int64).to(dev, non_blocking=True),
+            torch.tensor(n_p, dtype=torch.int32).to(dev, non_blocking=True),
+            self.V)
 
 
 class EngineWorker:
@@ -314,6 +446,9 @@ class EngineWorker:
         self._pending = None   # (reqs, event|None, n) — one-step readback lag
         self._pin_lp = None
         self._pending_lp = None   # logprobs of the pending step, if sampled
+        self.tstate = TokenStatePool(config.vocab_size, self.device)
+        self._pin_top = None      # (tokens i64, logprobs f32), [cap, 20]
+        self._pending_top = None  # top-N of the pending step, if asked for
         self.steps = 0
         self._rejects: List[RequestOutput] = []
         self._carry: List[RequestOutput] = []   # outputs surfaced early
@@ -456,6 +591,8 @@ class EngineWorker:
                         clamped=clamped)
             req.max_tokens = clamped
         self._resolve_seed(req)
+        if req.orig_prompt_len is None:
+            req.orig_prompt_len = len(req.prompt_tokens)
         self.waiting.append(req)
         self._by_id[req.request_id] = req
 
@@ -473,12 +610,15 @@ class EngineWorker:
 
     def admit_transferred(self, req: EngineRequest, local_blocks: List[int],
                           seq_len: int, first_token: int,
-                          first_logprob: Optional[float] = None) -> None:
+                          first_logprob: Optional[float] = None,
+                          first_top_logprobs: Optional[list] = None) -> None:
         """Adopt a prefilled sequence whose KV arrived over xGMI. The
         adopted full blocks are registered in the prefix cache: a
         transferred prefix is as reusable as a locally-computed one.
         first_logprob is the first token's logprob from the prefill side,
-        for a logprobs=True request."""
+        for a logprobs=True request, first_top_logprobs its top-N list. A
+        penalised request's token state is rebuilt here from the prompt and
+        the first token, which counts as output."""
         self.mgr.adopt(req.request_id, local_blocks, seq_len)
         if req.block_hashes is None:
             req.block_hashes = block_hashes(req.prompt_tokens,
@@ -491,6 +631,10 @@ class EngineWorker:
         req.computed = req.prompt_len
         req.generated = [first_token]
         req.logprob_vals = [] if first_logprob is None else [first_logprob]
+        req.top_logprob_vals = [] if first_top_logprobs is None \
+            else [[tuple(e) for e in first_top_logprobs]]
+        if req.orig_prompt_len is None:
+            req.orig_prompt_len = req.prompt_len
         if not req.first_token_t:
             req.first_token_t = time.time()
         if self.ttft_slo_ms is not None and req.arrival_t and \
@@ -498,7 +642,9 @@ class EngineWorker:
             req.slo_ok = False
         self._by_id[req.request_id] = req
         self.running.append(req)
-        self.dstate.join(req, local_blocks, seq_len, first_token)
+        self.tstate.fill([req])
+        self.dstate.join(req, local_blocks, seq_len, first_token,
+                         self.tstate.row_of.get(req.request_id, -1))
 
     def abort(self, request_id: str) -> None:
         req = self._by_id.pop(request_id, None)
@@ -509,6 +655,7 @@ class EngineWorker:
         if req in self.running:
             self.running.remove(req)
         self.dstate.leave(request_id)
+        self.tstate.free(request_id)
         self.mgr.free(request_id)
 
     # ------------------------------------------------------------------
@@ -764,9 +911,12 @@ class EngineWorker:
         return outputs
 
     def _finish_prefills(self, finishing, logits, outputs) -> None:
-        lps = None
+        lps = tops = None
         if any(r.uses_sampler for r in finishing):
-            tokens, lps = self._sample_first(logits, finishing)
+            # the first token is penalised against the prompt (and, after a
+            # preemption, against the output so far)
+            self.tstate.fill(finishing)
+            tokens, lps, tops = self._sample_first(logits, finishing)
         else:
             tokens = self._sample_host(logits,
                                        [r.temperature for r in finishing])
@@ -776,6 +926,10 @@ class EngineWorker:
             if req.logprobs and lps is not None:
                 new_lp = [lps[i]]
                 req.logprob_vals.append(lps[i])
+            new_top = None
+            if req.top_logprobs > 0 and tops is not None:
+                new_top = [tops[i][:req.top_logprobs]]
+                req.top_logprob_vals.append(new_top[0])
             if not req.first_token_t:     # preempted reqs keep their TTFT
                 req.first_token_t = now
                 if self.ttft_slo_ms is not None and req.arrival_t and \
@@ -791,7 +945,8 @@ class EngineWorker:
                     first_token=int(tok), prompt_tokens=req.prompt_len,
                     cached_tokens=req.cached_tokens,
                     ttft_ms=(now - req.arrival_t) * 1e3,
-                    new_logprobs=new_lp))
+                    new_logprobs=new_lp, new_top_logprobs=new_top))
+                self.tstate.free(req.request_id)
                 # blocks stay allocated until the transfer engine releases
                 self._by_id.pop(req.request_id, None)
             else:
@@ -800,11 +955,13 @@ class EngineWorker:
                     self.total_generated_slo += 1
                 self.running.append(req)
                 self.dstate.join(req, self.mgr.tables[req.request_id],
-                                 self.mgr.seq_lens[req.request_id], int(tok))
+                                 self.mgr.seq_lens[req.request_id], int(tok),
+                                 self.tstate.row_of.get(req.request_id, -1))
                 outputs.append(RequestOutput(
                     request_id=req.request_id, new_tokens=[int(tok)],
                     ttft_ms=(now - req.arrival_t) * 1e3,
-                    cached_tokens=req.cached_tokens, new_logprobs=new_lp))
+                    cached_tokens=req.cached_tokens, new_logprobs=new_lp,
+                    new_top_logprobs=new_top))
                 self.total_generated += 1
 
     def release_prefilled(self, request_id: str) -> None:
@@ -881,8 +1038,20 @@ class EngineWorker:
                             for r in active))
         logits = self.model.forward(batch, self.pool.tensor,
                                     kv_scales=self.pool.all_layer_scales())
-        lp = None
-        if any(r.uses_sampler for r in active):
+        lp = top = None
+        if any(r.uses_ext for r in active):
+            # as below, through sample_ext: it reads each row's penalties
+            # from the token state and counts the chosen token into it
+            sel = lambda t: t.index_select(0, rows_t)
+            n_top = max(r.top_logprobs for r in active)
+            tok, lp, _, _, top_t, top_l = ops.sample_ext(
+                logits, sel(st.temps), sel(st.top_k), sel(st.top_p),
+                sel(st.seed), lens + sel(st.pos_off), sel(st.rep),
+                sel(st.pres), sel(st.freq), sel(st.min_p), sel(st.top_n),
+                sel(st.state_row), self.tstate.tensor, n_top)
+            if n_top:
+                top = (top_t, top_l)
+        elif any(r.uses_sampler for r in active):
             # the fused sampler takes the whole step: T <= 0 rows go
             # through its greedy branch; `lens` is the pre-step length
             tok, lp, _, _ = ops.sample(
@@ -910,12 +1079,25 @@ class EngineWorker:
                     self._pin_lp = torch.empty(
                         st.capacity, dtype=torch.float32, pin_memory=True)
                 self._pin_lp[:n].copy_(lp, non_blocking=True)
+            if top is not None:
+                # so do the top-N alternatives
+                if self._pin_top is None or \
+                        self._pin_top[0].shape[0] < st.capacity:
+                    self._pin_top = (
+                        torch.empty((st.capacity, 20), dtype=torch.int64,
+                                    pin_memory=True),
+                        torch.empty((st.capacity, 20), dtype=torch.float32,
+                                    pin_memory=True))
+                w = top[0].shape[1]
+                self._pin_top[0][:n, :w].copy_(top[0], non_blocking=True)
+                self._pin_top[1][:n, :w].copy_(top[1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             self._pending = (active, ev, n)
         else:
             self._pending = (active, None, tok)
         self._pending_lp = lp
+        self._pending_top = top
         return prev + finals
 
     def _collect_pending(self) -> List[RequestOutput]:
@@ -923,17 +1105,24 @@ class EngineWorker:
             return []
         reqs, ev, payload = self._pending
         lp_t, self._pending_lp = self._pending_lp, None
+        top_t, self._pending_top = self._pending_top, None
         self._pending = None
-        lps = None
+        lps = tops = None
         if ev is not None:
             ev.synchronize()
             vals = self._pin[:payload].tolist()
             if lp_t is not None:
                 lps = self._pin_lp[:payload].tolist()
+            if top_t is not None:
+                w = top_t[0].shape[1]
+                tops = self._top_lists(self._pin_top[0][:payload, :w],
+                                       self._pin_top[1][:payload, :w])
         else:
             vals = payload.tolist()
             if lp_t is not None:
                 lps = lp_t.tolist()
+            if top_t is not None:
+                tops = self._top_lists(*top_t)
         outputs: List[RequestOutput] = []
         now = time.time()
         for i, (req, tok) in enumerate(zip(reqs, vals)):
@@ -955,11 +1144,16 @@ class EngineWorker:
                                 else "length")
             if req.logprobs and lps is not None:
                 out.new_logprobs = [lps[i]]
+            if req.top_logprobs > 0 and tops is not None:
+                out.new_top_logprobs = [tops[i][:req.top_logprobs]]
+                req.top_logprob_vals.append(out.new_top_logprobs[0])
             if finished:
                 n_gen = len(req.generated)
                 out.all_tokens = list(req.generated)
                 if req.logprobs:
                     out.all_logprobs = list(req.logprob_vals)
+                if req.top_logprobs > 0:
+                    out.all_top_logprobs = list(req.top_logprob_vals)
                 out.prompt_tokens = req.prompt_len
                 out.completion_tokens = n_gen
                 out.cached_tokens = req.cached_tokens
@@ -969,6 +1163,7 @@ class EngineWorker:
                 out.e2e_ms = (now - req.arrival_t) * 1e3
                 self.running.remove(req)
                 self.dstate.leave(req.request_id)
+                self.tstate.free(req.request_id)
                 self.mgr.free(req.request_id)
                 self._by_id.pop(req.request_id, None)
             outputs.append(out)
@@ -1016,6 +1211,7 @@ class EngineWorker:
                  generated=len(req.generated))
         self.running.remove(req)
         self.dstate.leave(req.request_id)
+        self.tstate.free(req.request_id)
         self.mgr.free(req.request_id)
         req.prompt_tokens = merged
         req.computed = 0
@@ -1037,10 +1233,13 @@ class EngineWorker:
             e2e_ms=(now - req.arrival_t) * 1e3)
         if req.logprobs:
             out.all_logprobs = list(req.logprob_vals)
+        if req.top_logprobs > 0:
+            out.all_top_logprobs = list(req.top_logprob_vals)
         if n_gen > 1:
             out.tpot_ms = (now - req.first_token_t) * 1e3 / (n_gen - 1)
         self.running.remove(req)
         self.dstate.leave(req.request_id)
+        self.tstate.free(req.request_id)
         self.mgr.free(req.request_id)
         self._by_id.pop(req.request_id, None)
         return out
@@ -1065,23 +1264,44 @@ class EngineWorker:
     def _sample_first(self, logits: torch.Tensor,
                       reqs: List[EngineRequest]):
         """First-token sampling through the fused sampler, on the logits
-        where they live: (tokens, logprobs) as host lists. The token's
-        completion index is len(req.generated): 0, or where a preempted
-        request left off."""
+        where they live: (tokens, logprobs, top-N lists or None) as host
+        lists. The token's completion index is len(req.generated): 0, or
+        where a preempted request left off. With a request that sets a
+        sample_ext field the call goes through ops.sample_ext, the token
+        state rows having been filled by the caller."""
         dev = logits.device
-        tok, lp, _, _ = ops.sample(
-            logits,
-            torch.tensor([r.temperature for r in reqs],
-                         dtype=torch.float32, device=dev),
-            torch.tensor([r.top_k for r in reqs], dtype=torch.int32,
-                         device=dev),
-            torch.tensor([r.top_p for r in reqs], dtype=torch.float32,
-                         device=dev),
-            torch.tensor([_as_i64(r._seed64) for r in reqs],
-                         dtype=torch.int64, device=dev),
-            torch.tensor([len(r.generated) for r in reqs],
-                         dtype=torch.int32, device=dev))
-        return tok.tolist(), lp.tolist()
+        f32, i32 = torch.float32, torch.int32
+        col = lambda f, dt: torch.tensor([f(r) for r in reqs], dtype=dt,
+                                         device=dev)
+        base = (logits,
+                col(lambda r: r.temperature, f32),
+                col(lambda r: r.top_k, i32),
+                col(lambda r: r.top_p, f32),
+                col(lambda r: _as_i64(r._seed64), torch.int64),
+                col(lambda r: len(r.generated), i32))
+        if not any(r.uses_ext for r in reqs):
+            tok, lp, _, _ = ops.sample(*base)
+            return tok.tolist(), lp.tolist(), None
+        n_top = max(r.top_logprobs for r in reqs)
+        tok, lp, _, _, top_t, top_l = ops.sample_ext(
+            *base,
+            col(lambda r: r.repetition_penalty, f32),
+            col(lambda r: r.presence_penalty, f32),
+            col(lambda r: r.frequency_penalty, f32),
+            col(lambda r: r.min_p, f32),
+            col(lambda r: r.top_logprobs, i32),
+            col(lambda r: self.tstate.row_of.get(r.request_id, -1), i32),
+            self.tstate.tensor, n_top)
+        tops = self._top_lists(top_t, top_l) if n_top else None
+        return tok.tolist(), lp.tolist(), tops
+
+    @staticmethod
+    def _top_lists(top_tokens: torch.Tensor, top_logprobs: torch.Tensor):
+        """[B, n] top-N outputs -> per row [(token id, logprob)], without
+        the -1 entries past a row's own N."""
+        return [[(t, l) for t, l in zip(tr, lr) if t >= 0]
+                for tr, lr in zip(top_tokens.tolist(),
+                                  top_logprobs.tolist())]
 
     def _sample_host(self, logits: torch.Tensor,
                      temps: List[float]) -> List[int]:

@@ -96,6 +96,40 @@ def _sampling_into(req: LLMRequest, top_p: Any, top_k: Any, seed: Any,
     return None
 
 
+def _is_num(v: Any) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _penalties_into(req: LLMRequest, data: Dict[str, Any]) -> Optional[str]:
+    """Validate and store presence_penalty, frequency_penalty,
+    repetition_penalty, min_p and top_logprobs (absent = off). Call after
+    req.logprobs is set: top_logprobs requires it."""
+    for name in ("presence_penalty", "frequency_penalty"):
+        v = data.get(name)
+        if v is not None:
+            if not _is_num(v) or not -2.0 <= float(v) <= 2.0:
+                return f"{name} must be a number in [-2, 2]"
+            setattr(req, name, float(v))
+    v = data.get("repetition_penalty")
+    if v is not None:
+        if not _is_num(v) or not 0.0 < float(v) < float("inf"):
+            return "repetition_penalty must be a number > 0"
+        req.repetition_penalty = float(v)
+    v = data.get("min_p")
+    if v is not None:
+        if not _is_num(v) or not 0.0 <= float(v) <= 1.0:
+            return "min_p must be a number in [0, 1]"
+        req.min_p = float(v)
+    v = data.get("top_logprobs")
+    if v is not None:
+        if not _is_int(v) or not 0 <= v <= 20:
+            return "top_logprobs must be an integer in [0, 20]"
+        if v > 0 and not req.logprobs:
+            return "top_logprobs requires logprobs"
+        req.top_logprobs = v
+    return None
+
+
 def _extract_mm_items(messages: List[Dict[str, Any]]) -> List[MultiModalItem]:
     items: List[MultiModalItem] = []
     for msg in messages:
@@ -160,6 +194,9 @@ class OpenAIParser(Parser):
         elif lp != 0:
             return ParseResult(
                 error="logprobs must be a boolean or an integer >= 0")
+        err = _penalties_into(req, data)
+        if err:
+            return ParseResult(error=err)
         if isinstance(data.get("stop_token_ids"), list):
             req.stop_token_ids = [int(t) for t in data["stop_token_ids"]]
         req.streaming = bool(data.get("stream", False))

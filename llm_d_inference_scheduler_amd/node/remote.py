@@ -100,6 +100,7 @@ class RemoteForwarder:
         return self._pool
 
     def forward(self, req: LLMRequest, base_url: str) -> None:
+        from .runner import ext_fields_of
         payload = {
             "request_id": req.request_id,
             "model": req.target_model or req.model,
@@ -108,7 +109,7 @@ class RemoteForwarder:
             "max_tokens": req.max_tokens,
             "temperature": req.temperature,
             "top_k": req.top_k, "top_p": req.top_p, "seed": req.seed,
-            "logprobs": req.logprobs,
+            "logprobs": req.logprobs, **ext_fields_of(req),
             "stop_token_ids": req.stop_token_ids,
             "priority": req.priority,
             "stream": bool(req.streaming),
@@ -134,7 +135,8 @@ class RemoteForwarder:
                 tokens=resp.get("tokens", []),
                 finish_reason=resp.get("finish_reason", "length"),
                 error=resp.get("error", ""),
-                token_logprobs=resp.get("token_logprobs"))
+                token_logprobs=resp.get("token_logprobs"),
+                token_top_logprobs=resp.get("token_top_logprobs"))
         except Exception as e:
             log.error("remote forward failed", url=url, err=str(e))
             comp = Completion(request_id=request_id, usage=Usage(),
@@ -170,7 +172,8 @@ class RemoteForwarder:
                 tokens=final.get("tokens", []),
                 finish_reason=final.get("finish_reason", "length"),
                 error=final.get("error", ""),
-                token_logprobs=final.get("token_logprobs"))
+                token_logprobs=final.get("token_logprobs"),
+                token_top_logprobs=final.get("token_top_logprobs"))
         except Exception as e:
             log.error("remote stream failed", url=url, err=str(e))
             comp = Completion(request_id=request_id, usage=Usage(),

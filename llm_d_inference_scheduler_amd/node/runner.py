@@ -161,6 +161,27 @@ class Completion:
     error: str = ""
     # one logprob per entry of tokens, for a logprobs=True request
     token_logprobs: Optional[List[float]] = None
+    # per token, the [(token id, logprob)] alternatives (top_logprobs > 0)
+    token_top_logprobs: Optional[List[list]] = None
+
+
+# sample_ext request fields: carried by name from LLMRequest through the
+# node messages to EngineRequest (absent in a message = off)
+EXT_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penalty",
+              "min_p", "top_logprobs")
+
+
+def ext_fields_of(obj) -> Dict[str, Any]:
+    """The sample_ext fields of a request object that are not off."""
+    off = {"repetition_penalty": 1.0}
+    return {f: getattr(obj, f) for f in EXT_FIELDS
+            if getattr(obj, f, off.get(f, 0)) != off.get(f, 0)}
+
+
+def ext_fields_from(m: Dict[str, Any]) -> Dict[str, Any]:
+    """The sample_ext fields a message carries, as EngineRequest /
+    LLMRequest keyword arguments."""
+    return {f: m[f] for f in EXT_FIELDS if m.get(f) is not None}
 
 
 class NodeRunner:
@@ -640,6 +661,7 @@ class NodeRunner:
                    "temperature": req.temperature,
                    "top_k": req.top_k, "top_p": req.top_p,
                    "seed": req.seed, "logprobs": req.logprobs,
+                   **ext_fields_of(req),
                    "is_embedding": req.is_embedding,
                    "stream": req.streaming,
                    "cached": self._cached_tokens(decision, decode_rank),
@@ -728,6 +750,7 @@ class NodeRunner:
             max_tokens=m["max_tokens"], temperature=m["temperature"],
             top_k=m.get("top_k", 0), top_p=m.get("top_p", 1.0),
             seed=m.get("seed"), logprobs=m.get("logprobs", False),
+            **ext_fields_from(m),
             is_embedding=m.get("is_embedding", False),
             cached_tokens=m.get("cached", 0),
             priority=m.get("priority", 0),
@@ -760,6 +783,7 @@ class NodeRunner:
                 max_tokens=m["max_tokens"], temperature=m["temperature"],
                 top_k=m.get("top_k", 0), top_p=m.get("top_p", 1.0),
                 seed=m.get("seed"), logprobs=m.get("logprobs", False),
+                **ext_fields_from(m),
                 cached_tokens=m.get("cached", 0),
                 priority=m.get("priority", 0),
                 stop_token_ids=m.get("stop"),
@@ -816,6 +840,9 @@ class NodeRunner:
             state["tokens"].extend(m.get("tokens", []))
             if m.get("token_logprobs") is not None:
                 state.setdefault("logprobs", []).extend(m["token_logprobs"])
+            if m.get("token_top_logprobs") is not None:
+                state.setdefault("top_logprobs", []).extend(
+                    m["token_top_logprobs"])
             if state["first_usage"] is None:
                 state["first_usage"] = usage
             orig = state["orig"]
@@ -829,7 +856,7 @@ class NodeRunner:
                     max_tokens=orig.max_tokens,
                     temperature=orig.temperature,
                     top_k=orig.top_k, top_p=orig.top_p, seed=orig.seed,
-                    logprobs=orig.logprobs,
+                    logprobs=orig.logprobs, **ext_fields_of(orig),
                     stop_token_ids=orig.stop_token_ids,
                     streaming=orig.streaming, headers=dict(orig.headers),
                     objective_name=orig.objective_name,
@@ -849,7 +876,8 @@ class NodeRunner:
                 request_id=m["req_id"], usage=usage,
                 tokens=state["tokens"],
                 finish_reason=m.get("finish_reason", "length"), error="",
-                token_logprobs=state.get("logprobs")))
+                token_logprobs=state.get("logprobs"),
+                token_top_logprobs=state.get("top_logprobs")))
             return
         self._chunked.pop(m["req_id"], None)
         if self.evictor is not None:
@@ -859,7 +887,8 @@ class NodeRunner:
             tokens=m.get("tokens", []),
             finish_reason=m.get("finish_reason", "length"),
             error=m.get("error", ""),
-            token_logprobs=m.get("token_logprobs")))
+            token_logprobs=m.get("token_logprobs"),
+            token_top_logprobs=m.get("token_top_logprobs")))
 
     # ---- encode stage (E/PD, E/P/D) ----
     def _run_encoder(self, max_jobs: int = 8) -> None:
@@ -986,7 +1015,8 @@ class NodeRunner:
                 self.engine.admit_transferred(pending["req"], local,
                                               job["seq_len"],
                                               job["first_token"],
-                                              job.get("first_logprob"))
+                                              job.get("first_logprob"),
+                                              job.get("first_top_logprobs"))
                 # true TTFT through the hand-off (connector_nixlv2.go
                 # true_ttft_ms span attr): first token is client-visible
                 # only once the decode side adopted the KV
@@ -1040,6 +1070,9 @@ class NodeRunner:
                     "first_token": out.first_token,
                     "first_logprob": (out.new_logprobs[0]
                                       if out.new_logprobs else None),
+                    "first_top_logprobs": (out.new_top_logprobs[0]
+                                           if out.new_top_logprobs
+                                           else None),
                     "ttft_ms": out.ttft_ms,
                     "kv_scales_id": self.engine.pool.scales_id})
             elif out.kind == "embedding" and out.finished:
@@ -1078,6 +1111,9 @@ class NodeRunner:
                "e2e_ms": out.e2e_ms, "error": out.error}
         if out.all_logprobs is not None:
             msg["token_logprobs"] = list(out.all_logprobs)
+        if out.all_top_logprobs is not None:
+            msg["token_top_logprobs"] = [list(map(list, t))
+                                         for t in out.all_top_logprobs]
         if self.is_router:
             self._handle_done(msg)
         else:

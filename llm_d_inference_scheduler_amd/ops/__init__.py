@@ -1,4 +1,5 @@
 from .dispatch import (  # noqa: F401
     flash_prefill, hip_ops, move_blocks, paged_attention, reshape_and_cache,
-    rmsnorm, rope, sample, silu_mul,
+    rmsnorm, rope, sample, sample_ext, silu_mul, token_state_alloc,
+    token_state_fill,
 )

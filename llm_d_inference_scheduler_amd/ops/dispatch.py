@@ -146,6 +146,43 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor,
     return ref.sample(logits, temperature, top_k, top_p, seed, pos)
 
 
+def sample_ext(logits: torch.Tensor, temperature: torch.Tensor,
+               top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
+               pos: torch.Tensor, rep: torch.Tensor, pres: torch.Tensor,
+               freq: torch.Tensor, min_p: torch.Tensor, top_n: torch.Tensor,
+               state_row: torch.Tensor,
+               state: Optional[torch.Tensor] = None, n_top: int = 0):
+    """sample() with repetition / presence / frequency penalties (rep, pres,
+    freq f32 [B]) read from the token state (int16 [R, Vs], row state_row[r]
+    or -1 for none; updated in place with the chosen token), min_p f32 [B]
+    and the top_n[r] <= n_top best raw logprobs -> (tokens, logprobs,
+    n_kept, threshold, top_tokens i64 [B, n_top], top_logprobs f32
+    [B, n_top]). Rows of one call must not share a state_row >= 0."""
+    if _use_hip(logits):
+        return _ext.sample_ext(logits.contiguous(), temperature, top_k,
+                               top_p, seed, pos, rep, pres, freq, min_p,
+                               top_n, state_row, state, n_top)
+    return ref.sample_ext(logits, temperature, top_k, top_p, seed, pos, rep,
+                          pres, freq, min_p, top_n, state_row, state, n_top)
+
+
+def token_state_alloc(rows: int, V: int, device) -> torch.Tensor:
+    """Zeroed token state for `rows` requests over a vocabulary of V."""
+    return ref.token_state_alloc(rows, V, device)
+
+
+def token_state_fill(state: torch.Tensor, rows: torch.Tensor,
+                     tokens: torch.Tensor, offsets: torch.Tensor,
+                     n_prompt: torch.Tensor, V: int) -> None:
+    """Rebuild state rows `rows` (i32 [n]) from token lists: entry q covers
+    tokens[offsets[q] : offsets[q + 1]] (tokens i32, offsets i64 [n + 1]),
+    its first n_prompt[q] (i32 [n]) ids being the prompt, the rest output."""
+    if _use_hip(state):
+        _ext.token_state_fill(state, rows, tokens, offsets, n_prompt, V)
+        return
+    ref.token_state_fill(state, rows, tokens, offsets, n_prompt, V)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

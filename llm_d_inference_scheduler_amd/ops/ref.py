@@ -5,6 +5,8 @@ runs) and (b) as the fp32 ground truth the GPU numerics tests compare the
 HIP kernels against (tests/test_gpu_kernels.py). Math is fp32 regardless of
 input dtype, mirroring the kernels' internal precision.
 """
+from typing import Optional
+
 import torch
 
 FP8_E4M3_MAX = 448.0
@@ -172,21 +174,27 @@ def gumbel_noise(idx: torch.Tensor, seed: int, pos: int) -> torch.Tensor:
 
 
 def _sample_row(l: torch.Tensor, T: float, k: int, p: float, seed: int,
-                pos: int):
-    """One row of sample(); l is fp32 [V]. Returns (token, logprob, n_kept,
+                pos: int, x: Optional[torch.Tensor] = None,
+                min_p: float = 0.0, minp_base=None):
+    """One row of sample() / sample_ext(); l is fp32 [V], x the penalised
+    logits of step 0 (None: x = l). minp_base(z, l * inv) gives the value
+    min_p is measured from (None: max z). Returns (token, logprob, n_kept,
     threshold, detail)."""
     V = l.shape[0]
     f32 = torch.float32
     M = l.max()
     lse = M + torch.log(torch.exp(l - M).sum(dtype=f32))
     detail = {"score_gap": float("inf"), "max_abs_z": 0.0,
-              "mass_margin": float("inf")}
+              "mass_margin": float("inf"), "minp_margin": float("inf"),
+              "lse": lse}
+    if x is None:
+        x = l
     T32 = torch.tensor(T, dtype=f32)
     if not T32 > 0:
-        tok = int(torch.nonzero(l == M)[0])
+        tok = int(torch.nonzero(x == x.max())[0])
         return tok, float(l[tok] - lse), V, float("-inf"), detail
     inv = torch.tensor(1.0, dtype=f32) / T32
-    z = l * inv
+    z = x * inv
     m = z.max()
     tau = torch.tensor(float("-inf"), dtype=f32)
     if 0 < k < V:
@@ -213,6 +221,13 @@ def _sample_row(l: torch.Tensor, T: float, k: int, p: float, seed: int,
             margin = min(margin, abs(float(target - cum_end[g - 1])))
         detail["mass_margin"] = margin / float(W)
         tau = torch.maximum(tau, tau_p)
+    mp32 = torch.tensor(min_p, dtype=f32)
+    if mp32 > 0:
+        base = m if minp_base is None else minp_base(z, l * inv)
+        # log(min_p) correctly rounded to fp32: through float64
+        tau_m = base + torch.log(mp32.double()).to(f32)
+        detail["minp_margin"] = float((z - tau_m).abs().min())
+        tau = torch.maximum(tau, tau_m)
     kept = torch.nonzero(z >= tau).squeeze(1)
     score = z[kept] + gumbel_noise(kept, seed, pos)
     best = int(torch.argmax(score))         # first maximum = lowest index
@@ -250,6 +265,159 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor,
            torch.tensor(nks, dtype=torch.int32, device=dev),
            torch.tensor(ths, dtype=torch.float32, device=dev))
     return out + (dets,) if details else out
+
+
+# ---- sample_ext: penalties, min_p, top-N, token state -----------------------
+
+STATE_COUNT_MASK = 0x3FFF           # c: occurrences in the output, saturating
+STATE_PROMPT_BIT = 0x4000           # bit 14: the token occurs in the prompt
+TOPN_MAX = 20
+
+
+def token_state_alloc(rows: int, V: int, device) -> torch.Tensor:
+    """A zeroed token state: int16 [rows, Vs], Vs = V rounded up to a
+    multiple of 8 (rows stay 16-byte aligned; columns >= V are padding)."""
+    return torch.zeros((rows, (V + 7) // 8 * 8), dtype=torch.int16,
+                       device=device)
+
+
+class SamplerExtModel:
+    """sample_ext / token_state_fill on CPU tensors, with the extension's
+    signatures. The small methods are the places where an implementation
+    can go wrong; tests/test_sampler_ext.py overrides them one at a time to
+    prove that the test cases notice."""
+
+    # -- step 0 --
+    def rep_mask(self, s):
+        """Elements the repetition penalty applies to (s: int32 state)."""
+        return s != 0
+
+    def rep_apply(self, x, rep):
+        return torch.where(x > 0, x / rep, x * rep)
+
+    def freq_count(self, s):
+        return (s & STATE_COUNT_MASK).to(torch.float32)
+
+    def pres_mask(self, s):
+        return (s & STATE_COUNT_MASK) > 0
+
+    def penalise(self, l, s, rep, pres, freq):
+        """x of step 0 for raw fp32 logits l and int32 state s, each torch
+        op one rounded fp32 operation."""
+        f32 = torch.float32
+        rep, pres, freq = (torch.tensor(v, dtype=f32)
+                           for v in (rep, pres, freq))
+        x = torch.where(self.rep_mask(s), self.rep_apply(l, rep), l)
+        x = x - freq * self.freq_count(s)
+        return x - torch.where(self.pres_mask(s), pres,
+                               torch.zeros((), dtype=f32))
+
+    # -- min_p --
+    def minp_base(self, z, z_raw):
+        return z.max()
+
+    # -- top-N --
+    def topn_values(self, l, x):
+        return l
+
+    def topn_pick(self, v, n):
+        """Indices of the n largest of v by (value descending, index
+        ascending)."""
+        return torch.argsort(v, descending=True, stable=True)[:n]
+
+    # -- state --
+    def bump(self, s: int) -> int:
+        """State element after one more occurrence in the output."""
+        return s if (s & STATE_COUNT_MASK) == STATE_COUNT_MASK else s + 1
+
+    def update_state(self, row, tok: int) -> None:
+        row[tok] = self.bump(int(row[tok]))
+
+    def sample_ext(self, logits, temperature, top_k, top_p, seed, pos, rep,
+                   pres, freq, min_p, top_n, state_row, state=None,
+                   n_top: int = 0, details: bool = False):
+        """sample() with the per-row extensions of DEVELOPMENT.md
+        "Sampling": rep / pres / freq / min_p [B] fp32, top_n / state_row
+        [B] int32, state the int16 token state [R, Vs] or None (updated in
+        place), n_top the width of the top-N outputs. Returns (tokens,
+        logprobs, n_kept, threshold, top_tokens [B, n_top] i64, top_logprobs
+        [B, n_top] f32), plus the per-row details with details=True."""
+        _req(0 <= n_top <= TOPN_MAX, "n_top must be in [0, 20]")
+        B, V = logits.shape
+        if state is not None:
+            _req(state.dtype == torch.int16 and state.dim() == 2 and
+                 state.shape[1] == (V + 7) // 8 * 8,
+                 "state must be int16 [R, Vs]")
+        lf = logits.detach().to("cpu", torch.float32)
+        toks, lps, nks, ths, dets = [], [], [], [], []
+        top_tok = torch.full((B, n_top), -1, dtype=torch.int64)
+        top_lp = torch.full((B, n_top), float("-inf"), dtype=torch.float32)
+        for r in range(B):
+            l = lf[r]
+            sr = int(state_row[r])
+            has = state is not None and 0 <= sr < state.shape[0]
+            s = state[sr, :V].to(torch.int32) if has else \
+                torch.zeros(V, dtype=torch.int32)
+            x = self.penalise(l, s, float(rep[r]), float(pres[r]),
+                              float(freq[r]))
+            tok, lp, nk, th, det = _sample_row(
+                l, float(temperature[r]), int(top_k[r]), float(top_p[r]),
+                int(seed[r]), int(pos[r]), x=x, min_p=float(min_p[r]),
+                minp_base=self.minp_base)
+            n = max(0, min(int(top_n[r]), n_top, V))
+            if n:
+                idx = self.topn_pick(self.topn_values(l, x) + 0.0, n)
+                top_tok[r, :n] = idx
+                top_lp[r, :n] = l[idx] - det["lse"]
+            if has:
+                self.update_state(state[sr], tok)
+            toks.append(tok); lps.append(lp); nks.append(nk); ths.append(th)
+            dets.append(det)
+        dev = logits.device
+        out = (torch.tensor(toks, dtype=torch.int64, device=dev),
+               torch.tensor(lps, dtype=torch.float32, device=dev),
+               torch.tensor(nks, dtype=torch.int32, device=dev),
+               torch.tensor(ths, dtype=torch.float32, device=dev),
+               top_tok.to(dev), top_lp.to(dev))
+        return out + (dets,) if details else out
+
+    def token_state_fill(self, state, rows, tokens, offsets, n_prompt,
+                         V: int) -> None:
+        """For each q: clear columns [0, V) of state row rows[q], set the
+        prompt bit for tokens[offsets[q] : offsets[q] + n_prompt[q]] and
+        count tokens[offsets[q] + n_prompt[q] : offsets[q + 1]], saturating.
+        Rows and ids out of range are skipped."""
+        _req(state.dtype == torch.int16 and state.dim() == 2 and
+             state.shape[1] == (V + 7) // 8 * 8,
+             "state must be int16 [R, Vs]")
+        _req(rows.dtype == torch.int32 and tokens.dtype == torch.int32 and
+             n_prompt.dtype == torch.int32,
+             "rows, tokens and n_prompt must be int32")
+        _req(offsets.dtype == torch.int64, "offsets must be int64")
+        _req(n_prompt.numel() == rows.numel() and
+             offsets.numel() == rows.numel() + 1,
+             "n_prompt must hold one value per row and offsets one more")
+        toks = tokens.tolist()
+        off = offsets.tolist()
+        for q, sr in enumerate(rows.tolist()):
+            if not 0 <= sr < state.shape[0]:
+                continue
+            beg = min(max(off[q], 0), len(toks))
+            end = min(max(off[q + 1], beg), len(toks))
+            n_p = min(max(int(n_prompt[q]), 0), end - beg)
+            vals = [0] * V
+            for t in toks[beg:beg + n_p]:
+                if 0 <= t < V:
+                    vals[t] |= STATE_PROMPT_BIT
+            for t in toks[beg + n_p:end]:
+                if 0 <= t < V:
+                    vals[t] = self.bump(vals[t])
+            state[sr, :V] = torch.tensor(vals, dtype=torch.int16)
+
+
+_SAMPLER_EXT = SamplerExtModel()
+sample_ext = _SAMPLER_EXT.sample_ext
+token_state_fill = _SAMPLER_EXT.token_state_fill
 
 
 # ---- prefix-cache kernels (contract: DEVELOPMENT.md "Prefix-cache tests") --

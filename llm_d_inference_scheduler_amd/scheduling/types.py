@@ -34,6 +34,11 @@ class LLMRequest:
     top_p: float = 1.0              # 1.0 = off
     seed: Optional[int] = None      # u64; None = engine-derived
     logprobs: bool = False          # return the sampled tokens' logprobs
+    repetition_penalty: float = 1.0     # > 0; 1.0 = off
+    presence_penalty: float = 0.0       # [-2, 2]; 0 = off
+    frequency_penalty: float = 0.0      # [-2, 2]; 0 = off
+    min_p: float = 0.0                  # [0, 1]; 0 = off
+    top_logprobs: int = 0               # 0..20 alternatives per token
     stop_token_ids: Optional[List[int]] = None
     streaming: bool = False
     is_embedding: bool = False

@@ -20,6 +20,7 @@ from fastapi.responses import JSONResponse, StreamingResponse
 from ..handlers.parsers import ParserMux, Usage
 from ..metrics import prom
 from ..models.tokenizer import HashTokenizer
+from ..node.runner import ext_fields_from
 from ..scheduling.types import LLMRequest
 from .service import NodeService
 
@@ -121,14 +122,21 @@ def build_app(service: NodeService,
         lps = completion.token_logprobs if req.logprobs else None
         pieces = [tok.decode([t]) for t in completion.tokens] \
             if lps is not None else []
+        # top_logprobs > 0: per token, [(token id, logprob)], best first
+        tops = completion.token_top_logprobs \
+            if lps is not None and req.top_logprobs > 0 else None
         if "chat" in path:
             choice = {"index": 0, "message":
                       {"role": "assistant", "content": text},
                       "finish_reason": completion.finish_reason}
             if lps is not None:
-                choice["logprobs"] = {"content": [
-                    {"token": p, "logprob": lp}
-                    for p, lp in zip(pieces, lps)]}
+                content = [{"token": p, "logprob": lp}
+                           for p, lp in zip(pieces, lps)]
+                for entry, alts in zip(content, tops or []):
+                    entry["top_logprobs"] = [
+                        {"token": tok.decode([int(t)]), "logprob": l}
+                        for t, l in alts]
+                choice["logprobs"] = {"content": content}
             return {"id": f"chatcmpl-{req.request_id}", "object":
                     "chat.completion", "created": created,
                     "model": req.model, "choices": [choice],
@@ -137,6 +145,11 @@ def build_app(service: NodeService,
                   "finish_reason": completion.finish_reason}
         if lps is not None:
             choice["logprobs"] = {"tokens": pieces, "token_logprobs": lps}
+            if tops is not None:
+                # (pieces that decode alike share a key: the best one wins)
+                choice["logprobs"]["top_logprobs"] = [
+                    {tok.decode([int(t)]): l for t, l in reversed(alts)}
+                    for alts in tops]
         return {"id": f"cmpl-{req.request_id}", "object": "text_completion",
                 "created": created, "model": req.model,
                 "choices": [choice], "usage": usage}
@@ -255,6 +268,7 @@ def build_app(service: NodeService,
             top_k=int(body.get("top_k") or 0),
             top_p=float(body.get("top_p") or 1.0),
             seed=body.get("seed"), logprobs=bool(body.get("logprobs")),
+            **ext_fields_from(body),
             stop_token_ids=body.get("stop_token_ids"),
             streaming=bool(body.get("stream", False)),
             priority=int(body.get("priority", 0)))
@@ -279,6 +293,8 @@ def build_app(service: NodeService,
                          "error": comp.error if comp else "lost",
                          "token_logprobs": (comp.token_logprobs
                                             if comp else None),
+                         "token_top_logprobs": (comp.token_top_logprobs
+                                                if comp else None),
                          "usage": {"prompt_tokens": u.prompt_tokens,
                                    "completion_tokens": u.completion_tokens,
                                    "cached_tokens": u.cached_tokens,
@@ -298,6 +314,7 @@ def build_app(service: NodeService,
                 "finish_reason": completion.finish_reason,
                 "error": completion.error,
                 "token_logprobs": completion.token_logprobs,
+                "token_top_logprobs": completion.token_top_logprobs,
                 "usage": {"prompt_tokens": u.prompt_tokens,
                           "completion_tokens": u.completion_tokens,
                           "cached_tokens": u.cached_tokens,
