@@ -14,8 +14,8 @@
 // and stored swizzled to LDS between a __syncthreads() pair, rows beyond
 // ctx zero-filled; each wave then attends the sub-tiles below its causal
 // horizon.
-#include "flash_prefill.h"
 #include "flash_tile.h"
+#include "launchers.h"
 
 namespace {
 
@@ -105,21 +105,12 @@ void flash_prefill_kernel(
 
 }  // namespace
 
-extern "C" {
-
-hipError_t lds_flash_prefill(const void* q, const void* k_cache,
-                             const void* v_cache,
-                             const int32_t* block_tables,
-                             const int32_t* seq_meta, const int32_t* tiles,
-                             void* out, int n_tiles, int n_q_heads, int kvh,
-                             int bs, int head_dim, int max_blocks, int kv_fp8,
-                             float scale, const float* k_scale,
-                             const float* v_scale, hipStream_t stream) {
-  if (n_tiles == 0) return hipSuccess;
-  if (head_dim != D) return hipErrorInvalidValue;
-  if (!kv_fp8 && (k_scale || v_scale)) return hipErrorInvalidValue;
-  dim3 grid(n_tiles, kvh), block(NW * WAVE);
-  const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
+hipError_t lds_flash_prefill(const AttnArgs& a, hipStream_t stream) {
+  if (a.n_tiles == 0) return hipSuccess;
+  if (a.head_dim != D) return hipErrorInvalidValue;
+  if (!a.kv_fp8 && (a.k_scale || a.v_scale)) return hipErrorInvalidValue;
+  dim3 grid(a.n_tiles, a.kvh), block(NW * WAVE);
+  const bool ok = dispatch_qpg(a.n_q_heads / a.kvh, [&](auto Q) {
     // ct: a value of the cache element type; scaled: std::true_type to
     // read the scales
     auto launch = [&](auto ct, auto scaled) {
@@ -127,17 +118,17 @@ hipError_t lds_flash_prefill(const void* q, const void* k_cache,
       hipLaunchKernelGGL(
           (flash_prefill_kernel<decltype(Q)::value, CT,
                                 decltype(scaled)::value>),
-          grid, block, 0, stream, (const short*)q, (const CT*)k_cache,
-          (const CT*)v_cache, block_tables, seq_meta, tiles, (short*)out,
-          k_scale, v_scale, kvh, bs, max_blocks, scale);
+          grid, block, 0, stream, (const short*)a.q, (const CT*)a.k_cache,
+          (const CT*)a.v_cache, a.block_tables, a.seq_meta, a.tiles,
+          (short*)a.out, a.k_scale, a.v_scale, a.kvh, a.bs, a.max_blocks,
+          a.scale);
     };
-    if (!kv_fp8) launch((short)0, std::false_type{});
-    else if (k_scale || v_scale) launch((unsigned char)0, std::true_type{});
+    if (!a.kv_fp8) launch((short)0, std::false_type{});
+    else if (a.k_scale || a.v_scale)
+      launch((unsigned char)0, std::true_type{});
     else launch((unsigned char)0, std::false_type{});
   });
   if (!ok) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
   return hipSuccess;
 }
-
-}  // extern "C"

@@ -18,8 +18,8 @@
 // launcher in ops.hip picks per cache dtype. The attention math, fragment
 // layouts and the swizzle are shared with that kernel (flash_tile.h); this
 // file is staging + ring loop + launcher.
-#include "flash_prefill.h"
 #include "flash_tile.h"
+#include "launchers.h"
 
 namespace {
 
@@ -133,26 +133,19 @@ __global__ __launch_bounds__(NW * WAVE, 2) void flash_prefill_glds_kernel(
 
 }  // namespace
 
-extern "C" {
-
-hipError_t lds_flash_prefill_glds(
-    const void* q, const void* k_cache, const void* v_cache,
-    const int32_t* block_tables, const int32_t* seq_meta,
-    const int32_t* tiles, void* out, int n_tiles, int n_q_heads, int kvh,
-    int bs, int head_dim, int max_blocks, float scale, hipStream_t stream) {
-  if (n_tiles == 0) return hipSuccess;
-  if (head_dim != D || max_blocks > BT_CAP) return hipErrorInvalidValue;
-  dim3 grid(n_tiles, kvh), block(NW * WAVE);
-  const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
+hipError_t lds_flash_prefill_glds(const AttnArgs& a, hipStream_t stream) {
+  if (a.n_tiles == 0) return hipSuccess;
+  if (a.head_dim != D || a.max_blocks > BT_CAP || a.kv_fp8)
+    return hipErrorInvalidValue;
+  dim3 grid(a.n_tiles, a.kvh), block(NW * WAVE);
+  const bool ok = dispatch_qpg(a.n_q_heads / a.kvh, [&](auto Q) {
     hipLaunchKernelGGL((flash_prefill_glds_kernel<decltype(Q)::value>), grid,
-                       block, 0, stream, (const short*)q,
-                       (const short*)k_cache, (const short*)v_cache,
-                       block_tables, seq_meta, tiles, (short*)out, kvh, bs,
-                       max_blocks, scale);
+                       block, 0, stream, (const short*)a.q,
+                       (const short*)a.k_cache, (const short*)a.v_cache,
+                       a.block_tables, a.seq_meta, a.tiles, (short*)a.out,
+                       a.kvh, a.bs, a.max_blocks, a.scale);
   });
   if (!ok) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
   return hipSuccess;
 }
-
-}  // extern "C"

@@ -7,6 +7,7 @@
 // MFMA-tile-aligned layout consumed zero-repack by both the decode attention
 // kernel and the xGMI transfer engine.
 #include "hip_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -55,15 +56,30 @@ __global__ void reshape_and_cache_kernel(const short* __restrict__ k_new,
   }
 }
 
-// Gather whole KV blocks (all layers, K+V) into a contiguous staging buffer
-// for an xGMI send:  staging: [n_sel, L, 2, KVH, BS, D].
-// pool: [L, 2, NB, KVH, BS, D]. block_ids: [n_sel].
-__global__ void gather_blocks_kernel(const short8* __restrict__ pool,
-                                     short8* __restrict__ staging,
-                                     const int32_t* __restrict__ block_ids,
-                                     int n_sel, int n_layers, int64_t nb,
-                                     int64_t block_elems8 /* KVH*BS*D/8 */) {
-  // one unit = one short8 chunk of one (sel, layer, kv) block copy
+// Move whole KV blocks (all layers, K+V) between pools and staging buffers.
+//   pool:    [L, 2, NB, KVH, BS, D], addressed through an id list [n_sel]
+//   staging: [n_sel, L, 2, KVH, BS, D], contiguous in unit order
+// One unit = one 16-byte short8 chunk of one (sel, layer, kv) block copy, so
+// unit i of a staging buffer is element i. SRC_BY_ID / DST_BY_ID say which
+// side is a pool:
+//   <true, false>  gather  pool blocks src_ids -> staging (xGMI send)
+//   <false, true>  scatter staging -> pool blocks dst_ids
+//   <true, true>   peer pull: blocks src_ids of a PEER GPU's pool (mapped via
+//                  hipIpcOpenMemHandle, so the loads travel over the direct
+//                  xGMI link) into this GPU's pool blocks dst_ids. One-sided:
+//                  no staging buffer, no send/recv rendezvous (SURVEY.md
+//                  §5.8 names hipMemcpyPeerAsync; a gather kernel over the
+//                  mapped peer pointer is the same xGMI path but handles
+//                  the non-contiguous block list in one launch).
+// The id list and block count of a staging side are not read.
+template <bool SRC_BY_ID, bool DST_BY_ID>
+__global__ void move_blocks_kernel(const short8* __restrict__ src,
+                                   short8* __restrict__ dst,
+                                   const int32_t* __restrict__ src_ids,
+                                   const int32_t* __restrict__ dst_ids,
+                                   int n_sel, int n_layers, int64_t src_nb,
+                                   int64_t dst_nb,
+                                   int64_t block_elems8 /* KVH*BS*D*size/16 */) {
   const int64_t per_sel = (int64_t)n_layers * 2 * block_elems8;
   const int64_t total = per_sel * n_sel;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -72,59 +88,37 @@ __global__ void gather_blocks_kernel(const short8* __restrict__ pool,
     int64_t rem = i % per_sel;
     int64_t lkv = rem / block_elems8;       // layer*2 + kv
     int64_t off = rem % block_elems8;
-    int64_t src_block = block_ids[sel];
-    staging[i] = pool[(lkv * nb + src_block) * block_elems8 + off];
+    int64_t s = i, d = i;
+    if constexpr (SRC_BY_ID)
+      s = (lkv * src_nb + src_ids[sel]) * block_elems8 + off;
+    if constexpr (DST_BY_ID)
+      d = (lkv * dst_nb + dst_ids[sel]) * block_elems8 + off;
+    dst[d] = src[s];
   }
 }
 
-// Scatter a staging buffer (same layout) into this GPU's pool blocks.
-__global__ void scatter_blocks_kernel(short8* __restrict__ pool,
-                                      const short8* __restrict__ staging,
-                                      const int32_t* __restrict__ block_ids,
-                                      int n_sel, int n_layers, int64_t nb,
-                                      int64_t block_elems8) {
-  const int64_t per_sel = (int64_t)n_layers * 2 * block_elems8;
-  const int64_t total = per_sel * n_sel;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t sel = i / per_sel;
-    int64_t rem = i % per_sel;
-    int64_t lkv = rem / block_elems8;
-    int64_t off = rem % block_elems8;
-    int64_t dst_block = block_ids[sel];
-    pool[(lkv * nb + dst_block) * block_elems8 + off] = staging[i];
-  }
-}
-
-// Direct peer-to-peer block copy: gather blocks `src_ids` straight out of a
-// PEER GPU's pool (mapped via hipIpcOpenMemHandle — loads travel over the
-// direct xGMI link) into this GPU's pool blocks `dst_ids`. One-sided pull:
-// no staging buffer, no send/recv rendezvous (SURVEY.md §5.8 names
-// hipMemcpyPeerAsync; a gather kernel over the mapped peer pointer is the
-// same xGMI path but handles the non-contiguous block list in one launch).
-__global__ void copy_blocks_peer_kernel(const short8* __restrict__ src_pool,
-                                        short8* __restrict__ dst_pool,
-                                        const int32_t* __restrict__ src_ids,
-                                        const int32_t* __restrict__ dst_ids,
-                                        int n_sel, int n_layers,
-                                        int64_t src_nb, int64_t dst_nb,
-                                        int64_t block_elems8) {
-  const int64_t per_sel = (int64_t)n_layers * 2 * block_elems8;
-  const int64_t total = per_sel * n_sel;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t sel = i / per_sel;
-    int64_t rem = i % per_sel;
-    int64_t lkv = rem / block_elems8;
-    int64_t off = rem % block_elems8;
-    dst_pool[(lkv * dst_nb + dst_ids[sel]) * block_elems8 + off] =
-        src_pool[(lkv * src_nb + src_ids[sel]) * block_elems8 + off];
-  }
+template <bool SRC_BY_ID, bool DST_BY_ID>
+hipError_t launch_move_blocks(const void* src, void* dst,
+                              const int32_t* src_ids, const int32_t* dst_ids,
+                              int n_sel, int n_layers, int64_t src_nb,
+                              int64_t dst_nb, int64_t block_bytes,
+                              hipStream_t stream) {
+  if (n_sel == 0) return hipSuccess;
+  // element-size agnostic: block_bytes is one (layer, K/V) block's bytes
+  const int64_t block_elems8 = block_bytes / 16;
+  const int64_t total = (int64_t)n_sel * n_layers * 2 * block_elems8;
+  const int threads = 256;
+  int blocks = (int)((total + threads - 1) / threads);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL((move_blocks_kernel<SRC_BY_ID, DST_BY_ID>), dim3(blocks),
+                     dim3(threads), 0, stream, (const short8*)src,
+                     (short8*)dst, src_ids, dst_ids, n_sel, n_layers, src_nb,
+                     dst_nb, block_elems8);
+  HIP_CHECK_LAST();
+  return hipSuccess;
 }
 
 }  // namespace
-
-extern "C" {
 
 hipError_t lds_reshape_and_cache(const void* k_new, const void* v_new,
                                  void* k_cache, void* v_cache,
@@ -157,25 +151,13 @@ hipError_t lds_gather_blocks(const void* pool, void* staging,
                              const int32_t* block_ids, int n_sel, int n_layers,
                              int64_t n_blocks, int64_t block_bytes,
                              int is_scatter, hipStream_t stream) {
-  // element-size agnostic: the kernels move 16-byte short8 units;
-  // block_bytes is one (layer, K/V) block's bytes (must be 16-aligned)
-  int64_t block_elems = block_bytes / 2;
-  if (n_sel == 0) return hipSuccess;
-  int64_t total = (int64_t)n_sel * n_layers * 2 * (block_elems / 8);
-  int threads = 256;
-  int blocks = (int)((total + threads - 1) / threads);
-  if (blocks > 4096) blocks = 4096;
-  if (is_scatter) {
-    hipLaunchKernelGGL(scatter_blocks_kernel, dim3(blocks), dim3(threads), 0,
-                       stream, (short8*)pool, (const short8*)staging, block_ids,
-                       n_sel, n_layers, n_blocks, block_elems / 8);
-  } else {
-    hipLaunchKernelGGL(gather_blocks_kernel, dim3(blocks), dim3(threads), 0,
-                       stream, (const short8*)pool, (short8*)staging, block_ids,
-                       n_sel, n_layers, n_blocks, block_elems / 8);
-  }
-  HIP_CHECK_LAST();
-  return hipSuccess;
+  if (is_scatter)
+    return launch_move_blocks<false, true>(staging, (void*)pool, nullptr,
+                                           block_ids, n_sel, n_layers, 0,
+                                           n_blocks, block_bytes, stream);
+  return launch_move_blocks<true, false>(pool, staging, block_ids, nullptr,
+                                         n_sel, n_layers, n_blocks, 0,
+                                         block_bytes, stream);
 }
 
 hipError_t lds_copy_blocks_peer(const void* src_pool, void* dst_pool,
@@ -183,18 +165,7 @@ hipError_t lds_copy_blocks_peer(const void* src_pool, void* dst_pool,
                                 int n_sel, int n_layers, int64_t src_nb,
                                 int64_t dst_nb, int64_t block_bytes,
                                 hipStream_t stream) {
-  if (n_sel == 0) return hipSuccess;
-  int64_t block_elems8 = block_bytes / 16;
-  int64_t total = (int64_t)n_sel * n_layers * 2 * block_elems8;
-  int threads = 256;
-  int blocks = (int)((total + threads - 1) / threads);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(copy_blocks_peer_kernel, dim3(blocks), dim3(threads), 0,
-                     stream, (const short8*)src_pool, (short8*)dst_pool,
-                     src_ids, dst_ids, n_sel, n_layers, src_nb, dst_nb,
-                     block_elems8);
-  HIP_CHECK_LAST();
-  return hipSuccess;
+  return launch_move_blocks<true, true>(src_pool, dst_pool, src_ids, dst_ids,
+                                        n_sel, n_layers, src_nb, dst_nb,
+                                        block_bytes, stream);
 }
-
-}  // extern "C"

@@ -6,6 +6,7 @@
 // pods (the router itself has no kernels); in the MI355X-native engine the
 // per-GPU worker runs them directly.
 #include "hip_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -14,11 +15,15 @@ namespace {
 //   if residual: r = r + x  (written back);  src = r
 //   else:        src = x
 //   y = src * rsqrt(mean(src^2) + eps) * w
-// One block (256 threads) per token row; row length H % 8 == 0.
+// One block (RMSNORM_WAVES waves = 256 threads) per token row; row length
+// H % 8 == 0. The launcher's block size and the kernel's reduction width
+// are both RMSNORM_WAVES.
 // Values are cached in registers between the sum-of-squares pass and the
 // normalize pass (up to CACHE_CHUNKS*8 elems/thread), avoiding a second HBM
 // read for H <= 256*CACHE_CHUNKS*8 (= 16384 at CACHE_CHUNKS=8).
 // ---------------------------------------------------------------------------
+constexpr int RMSNORM_WAVES = 4;
+
 template <bool RESIDUAL>
 __global__ void rmsnorm_kernel(const short* __restrict__ x,
                                short* __restrict__ residual,
@@ -59,7 +64,7 @@ __global__ void rmsnorm_kernel(const short* __restrict__ x,
       for (int j = 0; j < 8; ++j) vals[ci][j] = f[j];
     }
   }
-  float total = block_reduce_sum<4>(ss, red);
+  float total = block_reduce_sum<RMSNORM_WAVES>(ss, red);
   const float inv = rsqrtf(total / (float)H + eps);
 
   ci = 0;
@@ -140,12 +145,10 @@ __global__ void silu_mul_kernel(const short* __restrict__ gate_up,
 
 }  // namespace
 
-extern "C" {
-
 hipError_t lds_rmsnorm(const void* x, void* residual, const void* w, void* y,
                        int64_t n_rows, int H, float eps, hipStream_t stream) {
   if (n_rows == 0) return hipSuccess;
-  dim3 grid((uint32_t)n_rows), block(256);
+  dim3 grid((uint32_t)n_rows), block(RMSNORM_WAVES * WAVE);
   if (residual) {
     hipLaunchKernelGGL(rmsnorm_kernel<true>, grid, block, 0, stream,
                        (const short*)x, (short*)residual, (const short*)w,
@@ -184,5 +187,3 @@ hipError_t lds_silu_mul(const void* gate_up, void* y, int64_t T, int I,
   HIP_CHECK_LAST();
   return hipSuccess;
 }
-
-}  // extern "C"

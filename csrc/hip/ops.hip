@@ -9,7 +9,7 @@
 
 #include <climits>
 
-#include "flash_prefill.h"
+#include "launchers.h"
 
 #define CHECK_HIP(expr)                                                    \
   do {                                                                     \
@@ -18,49 +18,6 @@
   } while (0)
 
 #define CHECK_GPU(t) TORCH_CHECK((t).is_cuda() && (t).is_contiguous(), #t " must be contiguous on GPU")
-
-extern "C" {
-hipError_t lds_hash_prompts(const int32_t*, const int64_t*, int, int, int,
-                            uint64_t, uint64_t*, int32_t*, hipStream_t);
-hipError_t lds_table_update(uint64_t*, unsigned long long*, uint32_t,
-                            const uint64_t*, int64_t, int, int, unsigned int*,
-                            hipStream_t);
-hipError_t lds_match_longest(const uint64_t*, const unsigned long long*,
-                             uint32_t, const uint64_t*, const int32_t*, int,
-                             int, int, int32_t*, hipStream_t);
-hipError_t lds_rmsnorm(const void*, void*, const void*, void*, int64_t, int,
-                       float, hipStream_t);
-hipError_t lds_rope(void*, void*, const float*, const int32_t*, int, int, int,
-                    int, hipStream_t);
-hipError_t lds_silu_mul(const void*, void*, int64_t, int, hipStream_t);
-hipError_t lds_reshape_and_cache(const void*, const void*, void*, void*,
-                                 const int64_t*, int, int, int, int, int,
-                                 const float*, const float*, hipStream_t);
-hipError_t lds_gather_blocks(const void*, void*, const int32_t*, int, int,
-                             int64_t, int64_t, int, hipStream_t);
-hipError_t lds_paged_attention(const void*, const void*, const void*,
-                               const int32_t*, const int32_t*, void*, int, int,
-                               int, int, int, int, int, int, float,
-                               const float*, const float*, hipStream_t);
-hipError_t lds_paged_attention_split(const void*, const void*, const void*,
-                                     const int32_t*, const int32_t*, void*,
-                                     float*, float*, int, int, int, int, int,
-                                     int, int, int, int, int, float,
-                                     const float*, const float*, hipStream_t);
-hipError_t lds_sample(const void*, const float*, const int32_t*, const float*,
-                      const int64_t*, const int32_t*, int, int, int, int64_t*,
-                      float*, int32_t*, float*, hipStream_t);
-hipError_t lds_sample_ext(const void*, const float*, const int32_t*,
-                          const float*, const int64_t*, const int32_t*,
-                          const float*, const float*, const float*,
-                          const float*, const int32_t*, const int32_t*,
-                          int16_t*, int, int64_t, int, int, int, int, int64_t*,
-                          float*, int32_t*, float*, int64_t*, float*,
-                          hipStream_t);
-hipError_t lds_token_state_fill(int16_t*, int, int64_t, int, const int32_t*,
-                                int, const int32_t*, int64_t, const int64_t*,
-                                const int32_t*, hipStream_t);
-}
 
 namespace {
 
@@ -90,6 +47,54 @@ const float* kv_scale_ptr(const c10::optional<torch::Tensor>& s,
 hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
 }
+
+// ---- the argument contract (DEVELOPMENT.md "Op argument contract") ----
+// Every binding checks each argument with one of these before it allocates
+// or launches anything: the launchers and kernels trust what they get.
+
+// An integer argument or extent in [lo, hi] (hi <= INT_MAX), narrowed.
+int check_int(int64_t v, int64_t lo, int64_t hi, const char* name) {
+  TORCH_CHECK(v >= lo && v <= hi, name, " must be in [", lo, ", ", hi,
+              "], got ", v);
+  return (int)v;
+}
+
+// A tensor argument: on `anchor`'s device (a binding's first tensor is its
+// own anchor), of `dtype`, contiguous.
+void check_tensor(const torch::Tensor& t, const char* name,
+                  const torch::Tensor& anchor, const char* anchor_name,
+                  at::ScalarType dtype) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on a GPU");
+  TORCH_CHECK(t.device() == anchor.device(), name, " must be on ",
+              anchor_name, "'s device");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", dtype, ", got ",
+              t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// ... and of the rank of `shape`, with every extent that `shape` fixes.
+constexpr int64_t ANY = -1;
+
+std::string shape_str(at::IntArrayRef shape) {
+  std::string s = "[";
+  for (size_t i = 0; i < shape.size(); ++i)
+    s += (i ? ", " : "") + (shape[i] == ANY ? "*" : std::to_string(shape[i]));
+  return s + "]";
+}
+
+void check_tensor(const torch::Tensor& t, const char* name,
+                  const torch::Tensor& anchor, const char* anchor_name,
+                  at::ScalarType dtype, at::IntArrayRef shape) {
+  check_tensor(t, name, anchor, anchor_name, dtype);
+  bool ok = t.dim() == (int64_t)shape.size();
+  for (size_t i = 0; ok && i < shape.size(); ++i)
+    ok = shape[i] == ANY || t.size(i) == shape[i];
+  TORCH_CHECK(ok, name, " must have shape ", shape_str(shape), ", got ",
+              t.sizes());
+}
+
+// grid.y / grid.z limit: head counts and partitions ride there
+constexpr int64_t GRID_YZ_MAX = 65535;
 
 // ---- prefix-cache kernels ----
 
@@ -134,7 +139,7 @@ std::vector<torch::Tensor> hash_prompts(torch::Tensor tokens,
               "max_blocks must be >= 1, got ", max_blocks);
   TORCH_CHECK(offsets.numel() >= 1,
               "offsets must hold R+1 >= 1 values (request starts and the end)");
-  int n_req = (int)offsets.size(0) - 1;
+  int n_req = check_int(offsets.numel() - 1, 0, INT_MAX, "request count");
   auto hashes = torch::zeros({n_req, max_blocks},
                              tokens.options().dtype(torch::kUInt64));
   auto counts = torch::zeros({n_req}, tokens.options().dtype(torch::kInt32));
@@ -184,7 +189,7 @@ torch::Tensor match_longest(torch::Tensor keys, torch::Tensor masks,
               ") must hold one value per hashes row (", hashes.size(0), ")");
   TORCH_CHECK(n_endpoints >= 1 && n_endpoints <= 64,
               "n_endpoints must be in [1, 64], got ", n_endpoints);
-  int n_req = (int)hashes.size(0);
+  int n_req = check_int(hashes.size(0), 0, INT_MAX, "hashes.size(0)");
   auto out = torch::zeros({n_req, n_endpoints},
                           hashes.options().dtype(torch::kInt32));
   CHECK_HIP(lds_match_longest(
@@ -199,16 +204,19 @@ torch::Tensor match_longest(torch::Tensor keys, torch::Tensor masks,
 
 torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor w, double eps,
                       c10::optional<torch::Tensor> residual) {
-  CHECK_GPU(x); CHECK_GPU(w);
-  TORCH_CHECK(x.dtype() == torch::kBFloat16, "rmsnorm expects bf16");
-  auto y = torch::empty_like(x);
-  int H = (int)x.size(-1);
-  int64_t rows = x.numel() / H;
+  check_tensor(x, "x", x, "x", at::kBFloat16);
+  TORCH_CHECK(x.dim() >= 1, "x must have at least one dimension");
+  const int64_t H64 = x.size(-1);
+  TORCH_CHECK(H64 % 8 == 0, "x.size(-1) must be a multiple of 8, got ", H64);
+  const int H = check_int(H64, 8, INT_MAX, "x.size(-1)");
+  const int64_t rows = check_int(x.numel() / H, 0, INT_MAX, "rows of x");
+  check_tensor(w, "w", x, "x", at::kBFloat16, {H});
   void* res_ptr = nullptr;
   if (residual.has_value()) {
-    CHECK_GPU(*residual);
+    check_tensor(*residual, "residual", x, "x", at::kBFloat16, x.sizes());
     res_ptr = residual->data_ptr();
   }
+  auto y = torch::empty_like(x);
   CHECK_HIP(lds_rmsnorm(x.data_ptr(), res_ptr, w.data_ptr(), y.data_ptr(),
                         rows, H, (float)eps, cur_stream()));
   return y;
@@ -216,22 +224,32 @@ torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor w, double eps,
 
 void rope(torch::Tensor q, torch::Tensor k, torch::Tensor cos_sin,
           torch::Tensor positions) {
-  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(cos_sin); CHECK_GPU(positions);
-  int T = (int)q.size(0);
-  int qh = (int)q.size(1), kvh = (int)k.size(1), d = (int)q.size(2);
+  check_tensor(q, "q", q, "q", at::kBFloat16, {ANY, ANY, ANY});
+  const int64_t T = q.size(0), D = q.size(2);
+  TORCH_CHECK(D % 2 == 0, "head dim q.size(2) must be even, got ", D);
+  const int d = check_int(D, 2, 2048, "head dim q.size(2)");
+  check_tensor(k, "k", q, "q", at::kBFloat16, {T, ANY, D});
+  check_tensor(cos_sin, "cos_sin", q, "q", at::kFloat, {ANY, D / 2, 2});
+  check_tensor(positions, "positions", q, "q", at::kInt, {T});
+  check_int(q.size(1) + k.size(1), 1, GRID_YZ_MAX, "q heads + k heads");
   CHECK_HIP(lds_rope(q.data_ptr(), k.data_ptr(), cos_sin.data_ptr<float>(),
-                     positions.data_ptr<int32_t>(), T, qh, kvh, d,
-                     cur_stream()));
+                     positions.data_ptr<int32_t>(),
+                     check_int(T, 0, INT_MAX, "q.size(0)"), (int)q.size(1),
+                     (int)k.size(1), d, cur_stream()));
 }
 
 torch::Tensor silu_mul(torch::Tensor gate_up) {
-  CHECK_GPU(gate_up);
-  int64_t I2 = gate_up.size(-1);
+  check_tensor(gate_up, "gate_up", gate_up, "gate_up", at::kBFloat16);
+  TORCH_CHECK(gate_up.dim() >= 1, "gate_up must have at least one dimension");
+  const int64_t I2 = gate_up.size(-1);
+  TORCH_CHECK(I2 % 16 == 0, "gate_up.size(-1) must be 2*I with I a multiple "
+              "of 8, got ", I2);
+  const int I = check_int(I2 / 2, 8, INT_MAX, "I = gate_up.size(-1) / 2");
   int64_t T = gate_up.numel() / I2;
   auto sizes = gate_up.sizes().vec();
-  sizes.back() = I2 / 2;
+  sizes.back() = I;
   auto y = torch::empty(sizes, gate_up.options());
-  CHECK_HIP(lds_silu_mul(gate_up.data_ptr(), y.data_ptr(), T, (int)(I2 / 2),
+  CHECK_HIP(lds_silu_mul(gate_up.data_ptr(), y.data_ptr(), T, I,
                          cur_stream()));
   return y;
 }
@@ -241,30 +259,56 @@ void reshape_and_cache(torch::Tensor k_new, torch::Tensor v_new,
                        torch::Tensor slots,
                        c10::optional<torch::Tensor> k_inv_scale,
                        c10::optional<torch::Tensor> v_inv_scale) {
-  CHECK_GPU(k_new); CHECK_GPU(v_new); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
-  CHECK_GPU(slots);
+  check_tensor(k_new, "k_new", k_new, "k_new", at::kBFloat16,
+               {ANY, ANY, ANY});
+  const int64_t T = k_new.size(0), KVH = k_new.size(1), D = k_new.size(2);
+  TORCH_CHECK(D % 8 == 0, "head dim k_new.size(2) must be a multiple of 8, "
+              "got ", D);
+  check_int(KVH * (D / 8), 1, INT_MAX, "KVH * D / 8");
+  check_tensor(v_new, "v_new", k_new, "k_new", at::kBFloat16, {T, KVH, D});
+  const int fp8 = kv_fp8_flag(k_cache);
+  check_tensor(k_cache, "k_cache", k_new, "k_new", k_cache.scalar_type(),
+               {ANY, KVH, ANY, D});
+  check_tensor(v_cache, "v_cache", k_new, "k_new", k_cache.scalar_type(),
+               k_cache.sizes());
+  const int bs = check_int(k_cache.size(2), 1, INT_MAX,
+                           "block size k_cache.size(2)");
+  check_tensor(slots, "slots", k_new, "k_new", at::kLong, {T});
   const float* kis = kv_scale_ptr(k_inv_scale, k_cache, "k_inv_scale");
   const float* vis = kv_scale_ptr(v_inv_scale, v_cache, "v_inv_scale");
-  int T = (int)k_new.size(0), kvh = (int)k_new.size(1), d = (int)k_new.size(2);
-  int bs = (int)k_cache.size(2);
-  CHECK_HIP(lds_reshape_and_cache(k_new.data_ptr(), v_new.data_ptr(),
-                                  k_cache.data_ptr(), v_cache.data_ptr(),
-                                  slots.data_ptr<int64_t>(), T, kvh, bs, d,
-                                  kv_fp8_flag(k_cache), kis, vis,
-                                  cur_stream()));
+  CHECK_HIP(lds_reshape_and_cache(
+      k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(),
+      v_cache.data_ptr(), slots.data_ptr<int64_t>(),
+      check_int(T, 0, INT_MAX, "k_new.size(0)"), (int)KVH, bs, (int)D, fp8,
+      kis, vis, cur_stream()));
+}
+
+// The KV pool of move_blocks / copy_blocks_peer: [L, 2, NB, KVH, BS, D] on
+// a GPU, contiguous, one (layer, K/V) block a whole number of the 16-byte
+// units the mover copies. Returns that block's bytes.
+int64_t check_pool(const torch::Tensor& pool, const char* name) {
+  check_tensor(pool, name, pool, name, pool.scalar_type(),
+               {ANY, 2, ANY, ANY, ANY, ANY});
+  TORCH_CHECK(pool.size(0) <= INT_MAX, name, " has too many layers (",
+              pool.size(0), ")");
+  const int64_t block_bytes = pool.size(3) * pool.size(4) * pool.size(5) *
+                              (int64_t)pool.element_size();
+  TORCH_CHECK(block_bytes % 16 == 0, name, ": one block (", block_bytes,
+              " bytes) must be a multiple of 16 bytes");
+  return block_bytes;
 }
 
 void move_blocks(torch::Tensor pool, torch::Tensor staging,
                  torch::Tensor block_ids, bool is_scatter) {
-  CHECK_GPU(pool); CHECK_GPU(staging); CHECK_GPU(block_ids);
-  // pool: [L, 2, NB, KVH, BS, D]; staging: [n, L, 2, KVH, BS, D]
-  int L = (int)pool.size(0);
-  int64_t nb = pool.size(2);
-  int64_t block_bytes = pool.size(3) * pool.size(4) * pool.size(5) *
-                        pool.element_size();
+  const int64_t block_bytes = check_pool(pool, "pool");
+  check_tensor(block_ids, "block_ids", pool, "pool", at::kInt, {ANY});
+  const int64_t n = block_ids.size(0);
+  check_tensor(staging, "staging", pool, "pool", pool.scalar_type(),
+               {n, pool.size(0), 2, pool.size(3), pool.size(4), pool.size(5)});
   CHECK_HIP(lds_gather_blocks(pool.data_ptr(), staging.data_ptr(),
                               block_ids.data_ptr<int32_t>(),
-                              (int)block_ids.size(0), L, nb, block_bytes,
+                              check_int(n, 0, INT_MAX, "block_ids.size(0)"),
+                              (int)pool.size(0), pool.size(2), block_bytes,
                               is_scatter ? 1 : 0, cur_stream()));
 }
 
@@ -310,22 +354,90 @@ void ipc_close(uintptr_t ptr) {
   CHECK_HIP(hipIpcCloseMemHandle(reinterpret_cast<void*>(ptr)));
 }
 
-extern "C" hipError_t lds_copy_blocks_peer(const void*, void*, const int32_t*,
-                                           const int32_t*, int, int, int64_t,
-                                           int64_t, int64_t, hipStream_t);
-
+// src_pool_ptr: a peer pool [L, 2, src_nb, KVH, BS, D] mapped by ipc_open
+// (or this process's own pool), of dst_pool's layout apart from src_nb.
 void copy_blocks_peer(uintptr_t src_pool_ptr, torch::Tensor dst_pool,
                       torch::Tensor src_ids, torch::Tensor dst_ids,
                       int64_t src_nb) {
-  CHECK_GPU(dst_pool); CHECK_GPU(src_ids); CHECK_GPU(dst_ids);
-  int L = (int)dst_pool.size(0);
-  int64_t dst_nb = dst_pool.size(2);
-  int64_t block_bytes = dst_pool.size(3) * dst_pool.size(4) *
-                        dst_pool.size(5) * dst_pool.element_size();
+  TORCH_CHECK(src_pool_ptr != 0, "src_pool_ptr must not be null");
+  const int64_t block_bytes = check_pool(dst_pool, "dst_pool");
+  TORCH_CHECK(src_nb >= 1, "src_nb must be >= 1, got ", src_nb);
+  check_tensor(src_ids, "src_ids", dst_pool, "dst_pool", at::kInt, {ANY});
+  check_tensor(dst_ids, "dst_ids", dst_pool, "dst_pool", at::kInt, {ANY});
+  TORCH_CHECK(src_ids.size(0) == dst_ids.size(0), "src_ids (",
+              src_ids.size(0), ") and dst_ids (", dst_ids.size(0),
+              ") must be equally long");
   CHECK_HIP(lds_copy_blocks_peer(
       reinterpret_cast<const void*>(src_pool_ptr), dst_pool.data_ptr(),
       src_ids.data_ptr<int32_t>(), dst_ids.data_ptr<int32_t>(),
-      (int)src_ids.size(0), L, src_nb, dst_nb, block_bytes, cur_stream()));
+      check_int(src_ids.size(0), 0, INT_MAX, "src_ids.size(0)"),
+      (int)dst_pool.size(0), src_nb, dst_pool.size(2), block_bytes,
+      cur_stream()));
+}
+
+// ---- attention ----
+
+// What the three attention bindings share: q [N, QH, 128] bf16; the caches
+// [NB, KVH, BS, 128], alike, bf16 or fp8; QH = 1, 2, 4 or 8 times KVH;
+// block_tables [B, MB >= 1] int32; the optional fp8 scales. Returns the
+// launch arguments with everything but `out` and the decode / prefill group
+// filled in.
+AttnArgs check_attention(const torch::Tensor& q, const torch::Tensor& k_cache,
+                         const torch::Tensor& v_cache,
+                         const torch::Tensor& block_tables, double scale,
+                         const c10::optional<torch::Tensor>& k_scale,
+                         const c10::optional<torch::Tensor>& v_scale) {
+  AttnArgs a{};
+  check_tensor(q, "q", q, "q", at::kBFloat16, {ANY, ANY, 128});
+  check_int(q.size(0), 0, INT_MAX, "q.size(0)");
+  a.kv_fp8 = kv_fp8_flag(k_cache);
+  check_tensor(k_cache, "k_cache", q, "q", k_cache.scalar_type(),
+               {ANY, ANY, ANY, 128});
+  check_tensor(v_cache, "v_cache", q, "q", k_cache.scalar_type(),
+               k_cache.sizes());
+  a.kvh = check_int(k_cache.size(1), 1, GRID_YZ_MAX, "KV heads");
+  a.bs = check_int(k_cache.size(2), 1, INT_MAX, "block size k_cache.size(2)");
+  const int64_t QH = q.size(1), qpg = QH / a.kvh;
+  TORCH_CHECK(QH % a.kvh == 0 &&
+              (qpg == 1 || qpg == 2 || qpg == 4 || qpg == 8),
+              "q heads (", QH, ") must be 1, 2, 4 or 8 times the KV heads (",
+              a.kvh, ")");
+  a.n_q_heads = (int)QH;
+  a.head_dim = 128;
+  check_tensor(block_tables, "block_tables", q, "q", at::kInt, {ANY, ANY});
+  a.max_blocks = check_int(block_tables.size(1), 1, INT_MAX,
+                           "max_blocks = block_tables.size(1)");
+  a.k_scale = kv_scale_ptr(k_scale, k_cache, "k_scale");
+  a.v_scale = kv_scale_ptr(v_scale, v_cache, "v_scale");
+  a.q = q.data_ptr();
+  a.k_cache = k_cache.data_ptr();
+  a.v_cache = v_cache.data_ptr();
+  a.block_tables = block_tables.data_ptr<int32_t>();
+  a.scale = (float)scale;
+  return a;
+}
+
+// Decode: one q row, one block_tables row and one seq_lens entry per
+// sequence; chunk is the online-softmax chunk.
+AttnArgs check_decode(const torch::Tensor& q, const torch::Tensor& k_cache,
+                      const torch::Tensor& v_cache,
+                      const torch::Tensor& block_tables,
+                      const torch::Tensor& seq_lens, double scale,
+                      int64_t chunk,
+                      const c10::optional<torch::Tensor>& k_scale,
+                      const c10::optional<torch::Tensor>& v_scale) {
+  AttnArgs a = check_attention(q, k_cache, v_cache, block_tables, scale,
+                               k_scale, v_scale);
+  const int64_t B = block_tables.size(0);
+  TORCH_CHECK(q.size(0) == B, "q (", q.size(0), " rows) and block_tables (",
+              B, " rows) must hold one row per sequence");
+  check_tensor(seq_lens, "seq_lens", q, "q", at::kInt, {B});
+  TORCH_CHECK(chunk == 256 || chunk == 512, "chunk must be 256 or 512, got ",
+              chunk);
+  a.seq_lens = seq_lens.data_ptr<int32_t>();
+  a.n_seqs = (int)B;
+  a.chunk = (int)chunk;
+  return a;
 }
 
 torch::Tensor paged_attention(torch::Tensor q, torch::Tensor k_cache,
@@ -335,19 +447,11 @@ torch::Tensor paged_attention(torch::Tensor q, torch::Tensor k_cache,
                               int64_t chunk,
                               c10::optional<torch::Tensor> k_scale,
                               c10::optional<torch::Tensor> v_scale) {
-  CHECK_GPU(q); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
-  CHECK_GPU(block_tables); CHECK_GPU(seq_lens);
-  const float* ks = kv_scale_ptr(k_scale, k_cache, "k_scale");
-  const float* vs = kv_scale_ptr(v_scale, v_cache, "v_scale");
-  int B = (int)q.size(0), qh = (int)q.size(1), d = (int)q.size(2);
-  int kvh = (int)k_cache.size(1), bs = (int)k_cache.size(2);
+  AttnArgs a = check_decode(q, k_cache, v_cache, block_tables, seq_lens,
+                            scale, chunk, k_scale, v_scale);
   auto out = torch::empty_like(q);
-  CHECK_HIP(lds_paged_attention(
-      q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-      block_tables.data_ptr<int32_t>(), seq_lens.data_ptr<int32_t>(),
-      out.data_ptr(), B, qh, kvh, bs, d, (int)block_tables.size(1),
-      kv_fp8_flag(k_cache), (int)chunk, (float)scale, ks, vs,
-      cur_stream()));
+  a.out = out.data_ptr();
+  CHECK_HIP(lds_paged_attention(a, cur_stream()));
   return out;
 }
 
@@ -359,24 +463,20 @@ torch::Tensor paged_attention_split(torch::Tensor q, torch::Tensor k_cache,
                                     int64_t chunk,
                                     c10::optional<torch::Tensor> k_scale,
                                     c10::optional<torch::Tensor> v_scale) {
-  CHECK_GPU(q); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
-  CHECK_GPU(block_tables); CHECK_GPU(seq_lens);
-  const float* ks = kv_scale_ptr(k_scale, k_cache, "k_scale");
-  const float* vs = kv_scale_ptr(v_scale, v_cache, "v_scale");
-  int B = (int)q.size(0), qh = (int)q.size(1), d = (int)q.size(2);
-  int kvh = (int)k_cache.size(1), bs = (int)k_cache.size(2);
-  int qpg = qh / kvh;
+  AttnArgs a = check_decode(q, k_cache, v_cache, block_tables, seq_lens,
+                            scale, chunk, k_scale, v_scale);
+  // 64: the combine kernel's LDS table of per-partition scales
+  a.n_parts = check_int(n_parts, 1, 64, "n_parts");
+  a.part_tokens = check_int(part_tokens, 1, INT_MAX, "part_tokens");
+  const int qpg = a.n_q_heads / a.kvh;
   auto out = torch::empty_like(q);
   auto f32 = q.options().dtype(torch::kFloat32);
-  auto part_o = torch::empty({B, kvh, n_parts, qpg, d}, f32);
-  auto part_ml = torch::empty({B, kvh, n_parts, qpg, 2}, f32);
-  CHECK_HIP(lds_paged_attention_split(
-      q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-      block_tables.data_ptr<int32_t>(), seq_lens.data_ptr<int32_t>(),
-      out.data_ptr(), part_o.data_ptr<float>(), part_ml.data_ptr<float>(), B,
-      qh, kvh, bs, d, (int)block_tables.size(1), (int)n_parts,
-      (int)part_tokens, kv_fp8_flag(k_cache), (int)chunk, (float)scale, ks,
-      vs, cur_stream()));
+  auto part_o = torch::empty({a.n_seqs, a.kvh, n_parts, qpg, 128}, f32);
+  auto part_ml = torch::empty({a.n_seqs, a.kvh, n_parts, qpg, 2}, f32);
+  a.out = out.data_ptr();
+  a.part_o = part_o.data_ptr<float>();
+  a.part_ml = part_ml.data_ptr<float>();
+  CHECK_HIP(lds_paged_attention_split(a, cur_stream()));
   return out;
 }
 
@@ -386,14 +486,17 @@ torch::Tensor flash_prefill(torch::Tensor q, torch::Tensor k_cache,
                             double scale,
                             c10::optional<torch::Tensor> k_scale,
                             c10::optional<torch::Tensor> v_scale) {
-  CHECK_GPU(q); CHECK_GPU(k_cache); CHECK_GPU(v_cache);
-  CHECK_GPU(block_tables); CHECK_GPU(seq_meta); CHECK_GPU(tiles);
-  const float* ks = kv_scale_ptr(k_scale, k_cache, "k_scale");
-  const float* vs = kv_scale_ptr(v_scale, v_cache, "v_scale");
-  TORCH_CHECK(q.dtype() == torch::kBFloat16, "flash_prefill expects bf16");
-  int qh = (int)q.size(1), d = (int)q.size(2);
-  int kvh = (int)k_cache.size(1), bs = (int)k_cache.size(2);
+  AttnArgs a = check_attention(q, k_cache, v_cache, block_tables, scale,
+                               k_scale, v_scale);
+  // one (start, chunk, prior) row per block_tables row; tiles: (seq, vrow0)
+  check_tensor(seq_meta, "seq_meta", q, "q", at::kInt,
+               {block_tables.size(0), 3});
+  check_tensor(tiles, "tiles", q, "q", at::kInt, {ANY, 2});
+  a.seq_meta = seq_meta.data_ptr<int32_t>();
+  a.tiles = tiles.data_ptr<int32_t>();
+  a.n_tiles = check_int(tiles.size(0), 0, INT_MAX, "tiles.size(0)");
   auto out = torch::empty_like(q);
+  a.out = out.data_ptr();
   // bf16 KV rides the glds staging pipeline; fp8 needs convert-on-stage.
   // LLMD_NO_GLDS=1 forces the plain-VGPR kernel (bisect knob for the
   // cross-stream wedge investigation, profiles/r02_notes.md).
@@ -401,21 +504,10 @@ torch::Tensor flash_prefill(torch::Tensor q, torch::Tensor k_cache,
     const char* e = getenv("LLMD_NO_GLDS");
     return e && e[0] == '1';
   }();
-  if (!no_glds && !kv_fp8_flag(k_cache) &&
-      block_tables.size(1) <= FLASH_GLDS_BT_CAP) {
-    CHECK_HIP(lds_flash_prefill_glds(
-        q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-        block_tables.data_ptr<int32_t>(), seq_meta.data_ptr<int32_t>(),
-        tiles.data_ptr<int32_t>(), out.data_ptr(), (int)tiles.size(0), qh,
-        kvh, bs, d, (int)block_tables.size(1), (float)scale, cur_stream()));
-    return out;
-  }
-  CHECK_HIP(lds_flash_prefill(
-      q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-      block_tables.data_ptr<int32_t>(), seq_meta.data_ptr<int32_t>(),
-      tiles.data_ptr<int32_t>(), out.data_ptr(), (int)tiles.size(0), qh, kvh,
-      bs, d, (int)block_tables.size(1), kv_fp8_flag(k_cache), (float)scale,
-      ks, vs, cur_stream()));
+  if (!no_glds && !a.kv_fp8 && a.max_blocks <= FLASH_GLDS_BT_CAP)
+    CHECK_HIP(lds_flash_prefill_glds(a, cur_stream()));
+  else
+    CHECK_HIP(lds_flash_prefill(a, cur_stream()));
   return out;
 }
 
@@ -433,10 +525,12 @@ void check_sample_param(const torch::Tensor& t, const torch::Tensor& logits,
               t.numel());
 }
 
-std::vector<torch::Tensor> sample(torch::Tensor logits,
-                                  torch::Tensor temperature,
-                                  torch::Tensor top_k, torch::Tensor top_p,
-                                  torch::Tensor seed, torch::Tensor pos) {
+// What sample() and sample_ext() share: the checks of the logits and of
+// the five per-row vectors. Returns the launch arguments without outputs.
+SampleArgs check_sample(const torch::Tensor& logits,
+                        const torch::Tensor& temperature,
+                        const torch::Tensor& top_k, const torch::Tensor& top_p,
+                        const torch::Tensor& seed, const torch::Tensor& pos) {
   TORCH_CHECK(logits.is_cuda(), "logits must be on GPU");
   TORCH_CHECK(logits.dim() == 2, "logits must be [B, V]");
   TORCH_CHECK(logits.is_contiguous(), "logits must be contiguous");
@@ -450,19 +544,42 @@ std::vector<torch::Tensor> sample(torch::Tensor logits,
   check_sample_param(top_p, logits, at::kFloat, "top_p");
   check_sample_param(seed, logits, at::kLong, "seed");
   check_sample_param(pos, logits, at::kInt, "pos");
-  int B = (int)logits.size(0), V = (int)logits.size(1);
+  SampleArgs a{};
+  a.logits = logits.data_ptr();
+  a.temperature = temperature.data_ptr<float>();
+  a.top_k = top_k.data_ptr<int32_t>();
+  a.top_p = top_p.data_ptr<float>();
+  a.seed = seed.data_ptr<int64_t>();
+  a.pos = pos.data_ptr<int32_t>();
+  a.B = check_int(logits.size(0), 0, INT_MAX, "logits.size(0)");
+  a.V = (int)logits.size(1);
+  a.is_f32 = f32 ? 1 : 0;
+  return a;
+}
+
+// The four [B] outputs both samplers return, allocated and entered in `a`.
+std::vector<torch::Tensor> alloc_sample_out(SampleArgs& a,
+                                            const torch::Tensor& logits) {
   auto opt = logits.options();
-  auto tokens = torch::empty({B}, opt.dtype(torch::kInt64));
-  auto logprobs = torch::empty({B}, opt.dtype(torch::kFloat32));
-  auto n_kept = torch::empty({B}, opt.dtype(torch::kInt32));
-  auto threshold = torch::empty({B}, opt.dtype(torch::kFloat32));
-  CHECK_HIP(lds_sample(logits.data_ptr(), temperature.data_ptr<float>(),
-                       top_k.data_ptr<int32_t>(), top_p.data_ptr<float>(),
-                       seed.data_ptr<int64_t>(), pos.data_ptr<int32_t>(), B, V,
-                       f32 ? 1 : 0, tokens.data_ptr<int64_t>(),
-                       logprobs.data_ptr<float>(), n_kept.data_ptr<int32_t>(),
-                       threshold.data_ptr<float>(), cur_stream()));
+  auto tokens = torch::empty({a.B}, opt.dtype(torch::kInt64));
+  auto logprobs = torch::empty({a.B}, opt.dtype(torch::kFloat32));
+  auto n_kept = torch::empty({a.B}, opt.dtype(torch::kInt32));
+  auto threshold = torch::empty({a.B}, opt.dtype(torch::kFloat32));
+  a.tokens = tokens.data_ptr<int64_t>();
+  a.logprobs = logprobs.data_ptr<float>();
+  a.n_kept = n_kept.data_ptr<int32_t>();
+  a.threshold = threshold.data_ptr<float>();
   return {tokens, logprobs, n_kept, threshold};
+}
+
+std::vector<torch::Tensor> sample(torch::Tensor logits,
+                                  torch::Tensor temperature,
+                                  torch::Tensor top_k, torch::Tensor top_p,
+                                  torch::Tensor seed, torch::Tensor pos) {
+  SampleArgs a = check_sample(logits, temperature, top_k, top_p, seed, pos);
+  auto out = alloc_sample_out(a, logits);
+  CHECK_HIP(lds_sample(a, cur_stream()));
+  return out;
 }
 
 // The token state of sample_ext / token_state_fill: int16 [R, Vs] on
@@ -494,19 +611,7 @@ std::vector<torch::Tensor> sample_ext(
     torch::Tensor rep, torch::Tensor pres, torch::Tensor freq,
     torch::Tensor min_p, torch::Tensor top_n, torch::Tensor state_row,
     c10::optional<torch::Tensor> state, int64_t n_top) {
-  TORCH_CHECK(logits.is_cuda(), "logits must be on GPU");
-  TORCH_CHECK(logits.dim() == 2, "logits must be [B, V]");
-  TORCH_CHECK(logits.is_contiguous(), "logits must be contiguous");
-  const bool f32 = logits.scalar_type() == at::kFloat;
-  TORCH_CHECK(f32 || logits.scalar_type() == at::kBFloat16,
-              "logits must be bf16 or float32");
-  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) < (1LL << 31),
-              "vocabulary size out of range");
-  check_sample_param(temperature, logits, at::kFloat, "temperature");
-  check_sample_param(top_k, logits, at::kInt, "top_k");
-  check_sample_param(top_p, logits, at::kFloat, "top_p");
-  check_sample_param(seed, logits, at::kLong, "seed");
-  check_sample_param(pos, logits, at::kInt, "pos");
+  SampleArgs a = check_sample(logits, temperature, top_k, top_p, seed, pos);
   check_sample_param(rep, logits, at::kFloat, "rep");
   check_sample_param(pres, logits, at::kFloat, "pres");
   check_sample_param(freq, logits, at::kFloat, "freq");
@@ -515,35 +620,30 @@ std::vector<torch::Tensor> sample_ext(
   check_sample_param(state_row, logits, at::kInt, "state_row");
   TORCH_CHECK(n_top >= 0 && n_top <= 20, "n_top must be in [0, 20], got ",
               n_top);
-  int B = (int)logits.size(0), V = (int)logits.size(1);
-  int16_t* st = nullptr;
-  int R = 0;
-  int64_t Vs = 0;
+  ExtArgs ea{};
+  ea.rep = rep.data_ptr<float>();
+  ea.pres = pres.data_ptr<float>();
+  ea.freq = freq.data_ptr<float>();
+  ea.min_p = min_p.data_ptr<float>();
+  ea.top_n = top_n.data_ptr<int32_t>();
+  ea.state_row = state_row.data_ptr<int32_t>();
+  ea.n_top = (int)n_top;
   if (state.has_value()) {
-    check_token_state(*state, logits, V);
-    st = state->data_ptr<int16_t>();
-    R = (int)state->size(0);
-    Vs = state->size(1);
+    check_token_state(*state, logits, a.V);
+    ea.state = state->data_ptr<int16_t>();
+    ea.R = (int)state->size(0);
+    ea.Vs = state->size(1);
   }
+  auto out = alloc_sample_out(a, logits);
   auto opt = logits.options();
-  auto tokens = torch::empty({B}, opt.dtype(torch::kInt64));
-  auto logprobs = torch::empty({B}, opt.dtype(torch::kFloat32));
-  auto n_kept = torch::empty({B}, opt.dtype(torch::kInt32));
-  auto threshold = torch::empty({B}, opt.dtype(torch::kFloat32));
-  auto top_tokens = torch::empty({B, n_top}, opt.dtype(torch::kInt64));
-  auto top_logprobs = torch::empty({B, n_top}, opt.dtype(torch::kFloat32));
-  CHECK_HIP(lds_sample_ext(
-      logits.data_ptr(), temperature.data_ptr<float>(),
-      top_k.data_ptr<int32_t>(), top_p.data_ptr<float>(),
-      seed.data_ptr<int64_t>(), pos.data_ptr<int32_t>(),
-      rep.data_ptr<float>(), pres.data_ptr<float>(), freq.data_ptr<float>(),
-      min_p.data_ptr<float>(), top_n.data_ptr<int32_t>(),
-      state_row.data_ptr<int32_t>(), st, R, Vs, B, V, f32 ? 1 : 0,
-      (int)n_top, tokens.data_ptr<int64_t>(), logprobs.data_ptr<float>(),
-      n_kept.data_ptr<int32_t>(), threshold.data_ptr<float>(),
-      top_tokens.data_ptr<int64_t>(), top_logprobs.data_ptr<float>(),
-      cur_stream()));
-  return {tokens, logprobs, n_kept, threshold, top_tokens, top_logprobs};
+  auto top_tokens = torch::empty({a.B, n_top}, opt.dtype(torch::kInt64));
+  auto top_logprobs = torch::empty({a.B, n_top}, opt.dtype(torch::kFloat32));
+  ea.top_tokens = top_tokens.data_ptr<int64_t>();
+  ea.top_logprobs = top_logprobs.data_ptr<float>();
+  CHECK_HIP(lds_sample_ext(a, ea, cur_stream()));
+  out.push_back(top_tokens);
+  out.push_back(top_logprobs);
+  return out;
 }
 
 // Rebuild the listed state rows from token histories: for entry q, row

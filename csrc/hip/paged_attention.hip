@@ -21,6 +21,7 @@
 // writes an UNNORMALIZED partial (o_acc, m, l) and a tiny combine kernel
 // merges partitions: m* = max m_p; o = sum o_p*exp(m_p-m*); l likewise.
 #include "hip_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -297,92 +298,61 @@ __global__ __launch_bounds__(256) void paged_attention_combine_kernel(
 
 // ---- host launch plumbing ----
 
-struct PagedArgs {
-  dim3 grid;
-  hipStream_t stream;
-  const void *q, *k_cache, *v_cache;
-  const int32_t *block_tables, *seq_lens;
-  void* out;
-  float *part_o, *part_ml;  // null unless SPLIT
-  const float *k_scale, *v_scale;  // null = unscaled cache
-  int kvh, bs, max_blocks, part_tokens;
-  float scale;
-};
-
 template <int QPG, bool SPLIT, typename CT, int CHUNK>
-void launch_paged(const PagedArgs& a) {
-  hipLaunchKernelGGL((paged_attention_kernel<QPG, SPLIT, CT, CHUNK>), a.grid,
-                     dim3(NW * WAVE), 0, a.stream, (const short*)a.q,
+void launch_paged(const AttnArgs& a, hipStream_t stream) {
+  const dim3 grid(a.n_seqs, a.kvh, SPLIT ? a.n_parts : 1);
+  hipLaunchKernelGGL((paged_attention_kernel<QPG, SPLIT, CT, CHUNK>), grid,
+                     dim3(NW * WAVE), 0, stream, (const short*)a.q,
                      (const CT*)a.k_cache, (const CT*)a.v_cache,
-                     a.block_tables, a.seq_lens, (short*)a.out, a.part_o,
-                     a.part_ml, a.k_scale, a.v_scale, a.kvh, a.bs,
-                     a.max_blocks, a.part_tokens, a.scale);
+                     a.block_tables, a.seq_lens, (short*)a.out,
+                     SPLIT ? a.part_o : nullptr, SPLIT ? a.part_ml : nullptr,
+                     a.k_scale, a.v_scale, a.kvh, a.bs, a.max_blocks,
+                     SPLIT ? a.part_tokens : 0, a.scale);
 }
 
-// cache element type and online-softmax chunk (256 or 512, checked by the
-// callers) picked at run time
+// cache element type and online-softmax chunk picked at run time
 template <int QPG, bool SPLIT>
-void launch_paged(const PagedArgs& a, int kv_fp8, int chunk) {
-  if (kv_fp8) {
-    if (chunk == 512) launch_paged<QPG, SPLIT, unsigned char, 512>(a);
-    else launch_paged<QPG, SPLIT, unsigned char, 256>(a);
+void launch_paged(const AttnArgs& a, hipStream_t stream) {
+  if (a.kv_fp8) {
+    if (a.chunk == 512) launch_paged<QPG, SPLIT, unsigned char, 512>(a, stream);
+    else launch_paged<QPG, SPLIT, unsigned char, 256>(a, stream);
   } else {
-    if (chunk == 512) launch_paged<QPG, SPLIT, short, 512>(a);
-    else launch_paged<QPG, SPLIT, short, 256>(a);
+    if (a.chunk == 512) launch_paged<QPG, SPLIT, short, 512>(a, stream);
+    else launch_paged<QPG, SPLIT, short, 256>(a, stream);
   }
+}
+
+// what both decode launchers refuse (the binding has checked all of it)
+bool paged_args_ok(const AttnArgs& a) {
+  return a.head_dim == D && (a.chunk == 256 || a.chunk == 512) &&
+         (a.kv_fp8 || (!a.k_scale && !a.v_scale));
 }
 
 }  // namespace
 
-extern "C" {
-
-hipError_t lds_paged_attention(const void* q, const void* k_cache,
-                               const void* v_cache, const int32_t* block_tables,
-                               const int32_t* seq_lens, void* out, int n_seqs,
-                               int n_q_heads, int kvh, int bs, int head_dim,
-                               int max_blocks, int kv_fp8, int chunk,
-                               float scale, const float* k_scale,
-                               const float* v_scale, hipStream_t stream) {
-  if (n_seqs == 0) return hipSuccess;
-  if (head_dim != D) return hipErrorInvalidValue;
-  if (chunk != 256 && chunk != 512) return hipErrorInvalidValue;
-  if (!kv_fp8 && (k_scale || v_scale)) return hipErrorInvalidValue;
-  const PagedArgs a{dim3(n_seqs, kvh), stream, q, k_cache, v_cache,
-                    block_tables, seq_lens, out, nullptr, nullptr,
-                    k_scale, v_scale, kvh, bs, max_blocks, 0, scale};
-  const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
-    launch_paged<decltype(Q)::value, false>(a, kv_fp8, chunk);
+hipError_t lds_paged_attention(const AttnArgs& a, hipStream_t stream) {
+  if (a.n_seqs == 0) return hipSuccess;
+  if (!paged_args_ok(a)) return hipErrorInvalidValue;
+  const bool ok = dispatch_qpg(a.n_q_heads / a.kvh, [&](auto Q) {
+    launch_paged<decltype(Q)::value, false>(a, stream);
   });
   if (!ok) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
   return hipSuccess;
 }
 
-hipError_t lds_paged_attention_split(
-    const void* q, const void* k_cache, const void* v_cache,
-    const int32_t* block_tables, const int32_t* seq_lens, void* out,
-    float* part_o, float* part_ml, int n_seqs, int n_q_heads, int kvh, int bs,
-    int head_dim, int max_blocks, int n_parts, int part_tokens, int kv_fp8,
-    int chunk, float scale, const float* k_scale, const float* v_scale,
-    hipStream_t stream) {
-  if (n_seqs == 0) return hipSuccess;
-  if (head_dim != D || n_parts > 64) return hipErrorInvalidValue;
-  if (chunk != 256 && chunk != 512) return hipErrorInvalidValue;
-  if (!kv_fp8 && (k_scale || v_scale)) return hipErrorInvalidValue;
-  const PagedArgs a{dim3(n_seqs, kvh, n_parts), stream, q, k_cache, v_cache,
-                    block_tables, seq_lens, out, part_o, part_ml,
-                    k_scale, v_scale, kvh, bs, max_blocks, part_tokens,
-                    scale};
-  const bool ok = dispatch_qpg(n_q_heads / kvh, [&](auto Q) {
+hipError_t lds_paged_attention_split(const AttnArgs& a, hipStream_t stream) {
+  if (a.n_seqs == 0) return hipSuccess;
+  if (!paged_args_ok(a) || a.n_parts < 1 || a.n_parts > 64)
+    return hipErrorInvalidValue;
+  const bool ok = dispatch_qpg(a.n_q_heads / a.kvh, [&](auto Q) {
     constexpr int QPG = decltype(Q)::value;
-    launch_paged<QPG, true>(a, kv_fp8, chunk);
+    launch_paged<QPG, true>(a, stream);
     hipLaunchKernelGGL((paged_attention_combine_kernel<QPG>),
-                       dim3(n_seqs, kvh), dim3(256), 0, stream, part_o,
-                       part_ml, (short*)out, kvh, n_parts);
+                       dim3(a.n_seqs, a.kvh), dim3(256), 0, stream, a.part_o,
+                       a.part_ml, (short*)a.out, a.kvh, a.n_parts);
   });
   if (!ok) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
   return hipSuccess;
 }
-
-}  // extern "C"

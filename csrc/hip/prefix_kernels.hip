@@ -17,6 +17,7 @@
 // The chain definition is shared bit-exactly with the CPU core via
 // csrc/common/xxhash64.h.
 #include "hip_common.h"
+#include "launchers.h"
 #include "../common/xxhash64.h"
 
 using ldsr::block_content_hash;
@@ -205,8 +206,6 @@ __global__ void match_longest_kernel(const uint64_t* __restrict__ keys,
 
 // ---- host-side launchers (called from the torch binding) ----
 
-extern "C" {
-
 hipError_t lds_hash_prompts(const int32_t* tokens, const int64_t* offsets,
                             int n_requests, int block_tokens, int max_blocks,
                             uint64_t seed0, uint64_t* out, int32_t* counts,
@@ -251,5 +250,3 @@ hipError_t lds_match_longest(const uint64_t* keys,
   HIP_CHECK_LAST();
   return hipSuccess;
 }
-
-}  // extern "C"

@@ -27,6 +27,7 @@
 // the chosen token is counted into the state row. token_state_fill builds a
 // state row from a request's prompt and output so far.
 #include "hip_common.h"
+#include "launchers.h"
 
 #include <cfloat>
 #include <cmath>
@@ -183,21 +184,8 @@ template <typename T> struct Elem<T, true> {
   }
 };
 
-// What sample_ext adds to the launch; the plain sampler carries nothing.
-struct ExtArgs {
-  const float* rep;
-  const float* pres;
-  const float* freq;
-  const float* min_p;
-  const int32_t* top_n;
-  const int32_t* state_row;
-  short* state;              // [R, Vs] int16, or null: no row has state
-  int64_t Vs;
-  int R;
-  int n_top;                 // width of the top-N outputs, 0..TOPN_MAX
-  int64_t* top_tokens;       // [B, n_top]
-  float* top_logprobs;       // [B, n_top]
-};
+// sample_ext adds ExtArgs (launchers.h) to the launch; the plain sampler
+// carries nothing.
 struct NoExtArgs {};
 template <bool EXT> struct ExtArgsOf { typedef NoExtArgs type; };
 template <> struct ExtArgsOf<true> { typedef ExtArgs type; };
@@ -743,71 +731,48 @@ __global__ __launch_bounds__(FILL_THREADS) void token_state_fill_kernel(
   }
 }
 
+// One launch samples the whole batch: grid = B rows, no host sync.
+template <bool EXT>
+void launch_sample(const SampleArgs& a, typename ExtArgsOf<EXT>::type ea,
+                   hipStream_t stream) {
+  dim3 grid((uint32_t)a.B), block(SAMPLER_THREADS);
+  if (a.is_f32) {
+    hipLaunchKernelGGL((sample_kernel<float, EXT>), grid, block, 0, stream,
+                       (const float*)a.logits, a.temperature, a.top_k,
+                       a.top_p, a.seed, a.pos, a.V, a.tokens, a.logprobs,
+                       a.n_kept, a.threshold, ea);
+  } else {
+    hipLaunchKernelGGL((sample_kernel<short, EXT>), grid, block, 0, stream,
+                       (const short*)a.logits, a.temperature, a.top_k,
+                       a.top_p, a.seed, a.pos, a.V, a.tokens, a.logprobs,
+                       a.n_kept, a.threshold, ea);
+  }
+}
+
 }  // namespace
 
-extern "C" {
-
-// One launch samples the whole batch: grid = B rows, no host sync.
-// logits: [B, V] bf16 (is_f32 = 0) or fp32 (is_f32 = 1), rows contiguous.
-hipError_t lds_sample(const void* logits, const float* temperature,
-                      const int32_t* top_k, const float* top_p,
-                      const int64_t* seed, const int32_t* pos, int B, int V,
-                      int is_f32, int64_t* tokens, float* logprobs,
-                      int32_t* n_kept, float* threshold, hipStream_t stream) {
-  if (B == 0) return hipSuccess;
-  if (V <= 0) return hipErrorInvalidValue;
-  dim3 grid((uint32_t)B), block(SAMPLER_THREADS);
-  if (is_f32) {
-    hipLaunchKernelGGL((sample_kernel<float, false>), grid, block, 0, stream,
-                       (const float*)logits, temperature, top_k, top_p, seed,
-                       pos, V, tokens, logprobs, n_kept, threshold,
-                       NoExtArgs{});
-  } else {
-    hipLaunchKernelGGL((sample_kernel<short, false>), grid, block, 0, stream,
-                       (const short*)logits, temperature, top_k, top_p, seed,
-                       pos, V, tokens, logprobs, n_kept, threshold,
-                       NoExtArgs{});
-  }
+hipError_t lds_sample(const SampleArgs& a, hipStream_t stream) {
+  if (a.B == 0) return hipSuccess;
+  if (a.V <= 0) return hipErrorInvalidValue;
+  launch_sample<false>(a, NoExtArgs{}, stream);
   HIP_CHECK_LAST();
   return hipSuccess;
 }
 
 // sample with penalties, min_p, top-N and the token-state update
-// (DEVELOPMENT.md "Sampling"). state: [R, Vs] int16 or null; Vs % 8 == 0,
-// Vs >= V and the base 16-byte aligned (the binding checks). top_tokens /
-// top_logprobs: [B, n_top], n_top in [0, 20].
-hipError_t lds_sample_ext(const void* logits, const float* temperature,
-                          const int32_t* top_k, const float* top_p,
-                          const int64_t* seed, const int32_t* pos,
-                          const float* rep, const float* pres,
-                          const float* freq, const float* min_p,
-                          const int32_t* top_n, const int32_t* state_row,
-                          int16_t* state, int R, int64_t Vs, int B, int V,
-                          int is_f32, int n_top, int64_t* tokens,
-                          float* logprobs, int32_t* n_kept, float* threshold,
-                          int64_t* top_tokens, float* top_logprobs,
+// (DEVELOPMENT.md "Sampling").
+hipError_t lds_sample_ext(const SampleArgs& a, const ExtArgs& ea,
                           hipStream_t stream) {
-  if (B == 0) return hipSuccess;
-  if (V <= 0 || n_top < 0 || n_top > TOPN_MAX) return hipErrorInvalidValue;
-  if (state != nullptr && (Vs < V || Vs % 8 != 0 || R < 0))
+  if (a.B == 0) return hipSuccess;
+  if (a.V <= 0 || ea.n_top < 0 || ea.n_top > TOPN_MAX)
     return hipErrorInvalidValue;
-  ExtArgs ea{rep, pres, freq, min_p, top_n, state_row, (short*)state, Vs, R,
-             n_top, top_tokens, top_logprobs};
-  dim3 grid((uint32_t)B), block(SAMPLER_THREADS);
-  if (is_f32) {
-    hipLaunchKernelGGL((sample_kernel<float, true>), grid, block, 0, stream,
-                       (const float*)logits, temperature, top_k, top_p, seed,
-                       pos, V, tokens, logprobs, n_kept, threshold, ea);
-  } else {
-    hipLaunchKernelGGL((sample_kernel<short, true>), grid, block, 0, stream,
-                       (const short*)logits, temperature, top_k, top_p, seed,
-                       pos, V, tokens, logprobs, n_kept, threshold, ea);
-  }
+  if (ea.state != nullptr && (ea.Vs < a.V || ea.Vs % 8 != 0 || ea.R < 0))
+    return hipErrorInvalidValue;
+  launch_sample<true>(a, ea, stream);
   HIP_CHECK_LAST();
   return hipSuccess;
 }
 
-// state: [R, Vs] int16; rows, n_prompt: [n]; offsets: [n + 1] into toks.
 hipError_t lds_token_state_fill(int16_t* state, int R, int64_t Vs, int V,
                                 const int32_t* rows, int n,
                                 const int32_t* toks, int64_t n_toks,
@@ -821,5 +786,3 @@ hipError_t lds_token_state_fill(int16_t* state, int R, int64_t Vs, int V,
   HIP_CHECK_LAST();
   return hipSuccess;
 }
-
-}  // extern "C"

@@ -74,11 +74,13 @@ int main(int argc, char** argv) {
   hipMemcpy(dbt, hbt.data(), hbt.size() * 4, hipMemcpyHostToDevice);
   hipMemcpy(dmeta, hmeta.data(), hmeta.size() * 4, hipMemcpyHostToDevice);
   hipMemcpy(dtiles, htiles.data(), htiles.size() * 4, hipMemcpyHostToDevice);
-  hipError_t e = lds_flash_prefill(dq, dk, dv, dbt, dmeta, dtiles, dout,
-                                   (int)htiles.size() / 2, qh, kvh, BS, Dh,
-                                   nb, /*kv_fp8=*/0, 1.f / sqrtf(128.f),
-                                   /*k_scale=*/nullptr, /*v_scale=*/nullptr,
-                                   0);
+  AttnArgs a{};
+  a.q = dq; a.k_cache = dk; a.v_cache = dv; a.block_tables = dbt;
+  a.seq_meta = dmeta; a.tiles = dtiles; a.out = dout;
+  a.n_tiles = (int)htiles.size() / 2;
+  a.n_q_heads = qh; a.kvh = kvh; a.bs = BS; a.head_dim = Dh;
+  a.max_blocks = nb; a.scale = 1.f / sqrtf(128.f);
+  hipError_t e = lds_flash_prefill(a, 0);
   hipDeviceSynchronize();
   printf("launch: %s\n", hipGetErrorString(e));
   hipMemcpy(hout.data(), dout, hout.size() * 2, hipMemcpyDeviceToHost);
