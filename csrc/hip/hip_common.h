@@ -29,6 +29,21 @@ __device__ __forceinline__ short f32_to_bf16(float f) {
   return (short)(uint16_t)(rounded >> 16);
 }
 
+// NeoX rotate-half of one (x1, x2) = (x[i], x[i + D/2]) pair by the angle
+// whose (cos, sin) is (c, s). rope_kernel and qkv_rope_cache_kernel both
+// rotate through this one helper, so the two paths round alike. The fused
+// multiply-adds are written out: left to contraction, `x1*c - x2*s` is fused
+// one way in rope_kernel (the way below) and, once vectorised eight pairs
+// deep, comes out unfused for some pairs, which rounds differently.
+__device__ __forceinline__ void rope_rotate_pair(short x1_bf16, short x2_bf16,
+                                                 float c, float s, short& o1,
+                                                 short& o2) {
+  const float x1 = bf16_to_f32(x1_bf16);
+  const float x2 = bf16_to_f32(x2_bf16);
+  o1 = f32_to_bf16(__builtin_fmaf(x1, c, -(x2 * s)));
+  o2 = f32_to_bf16(__builtin_fmaf(x1, s, x2 * c));
+}
+
 // ---- fp8 (OCP e4m3) KV-cache element support ------------------------------
 // gfx950 hardware converts: v_cvt_f32_fp8 unpacks one byte of a dword
 // (constant byte select), v_cvt_pk_fp8_f32 packs two floats into half a

@@ -41,6 +41,18 @@ hipError_t lds_rope(void* q, void* k, const float* cos_sin,
 hipError_t lds_silu_mul(const void* gate_up, void* y, int64_t T, int I,
                         hipStream_t stream);
 
+// ---- qkv_epilogue.hip ----------------------------------------------------
+
+// qkv: [n_tokens, (n_q_heads + 2*kvh) * d] bf16 -> q_out [n_tokens,
+// n_q_heads, d] rotated; rotated K and plain V stored at slots[t] (< 0: not
+// stored). d % 16 == 0; every pointer 16-byte aligned.
+hipError_t lds_qkv_rope_cache(const void* qkv, const float* cos_sin,
+                              const int32_t* positions, const int64_t* slots,
+                              void* q_out, void* k_cache, void* v_cache,
+                              int64_t n_tokens, int n_q_heads, int kvh, int bs,
+                              int d, int kv_fp8, const float* k_inv_scale,
+                              const float* v_inv_scale, hipStream_t stream);
+
 // ---- kv_cache.hip --------------------------------------------------------
 
 hipError_t lds_reshape_and_cache(const void* k_new, const void* v_new,

@@ -109,10 +109,10 @@ __global__ void rope_kernel(short* __restrict__ q, short* __restrict__ k,
                     : k + ((int64_t)t * n_kv_heads + (head - n_q_heads)) * D;
   const float* cs = cos_sin + ((int64_t)positions[t] * half + lane) * 2;
   const float c = cs[0], s = cs[1];
-  float x1 = bf16_to_f32(base[lane]);
-  float x2 = bf16_to_f32(base[lane + half]);
-  base[lane] = f32_to_bf16(x1 * c - x2 * s);
-  base[lane + half] = f32_to_bf16(x2 * c + x1 * s);
+  short o1, o2;
+  rope_rotate_pair(base[lane], base[lane + half], c, s, o1, o2);
+  base[lane] = o1;
+  base[lane + half] = o2;
 }
 
 // ---------------------------------------------------------------------------

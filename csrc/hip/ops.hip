@@ -283,6 +283,57 @@ void reshape_and_cache(torch::Tensor k_new, torch::Tensor v_new,
       kis, vis, cur_stream()));
 }
 
+// The 16-byte accesses of qkv_rope_cache need their bases aligned.
+void check_aligned16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(((uintptr_t)t.data_ptr() & 15u) == 0, name,
+              " must be 16-byte aligned");
+}
+
+// The QKV GEMM's output row [q heads | k heads | v heads] -> rotated q
+// [T, QH, D]; rotated K and plain V go to the caches at slots[t] (a negative
+// slot stores nothing). Equals split + contiguous + rope + reshape_and_cache.
+torch::Tensor qkv_rope_cache(torch::Tensor qkv, torch::Tensor cos_sin,
+                             torch::Tensor positions, torch::Tensor slots,
+                             torch::Tensor k_cache, torch::Tensor v_cache,
+                             int64_t n_q_heads,
+                             c10::optional<torch::Tensor> k_inv_scale,
+                             c10::optional<torch::Tensor> v_inv_scale) {
+  check_tensor(qkv, "qkv", qkv, "qkv", at::kBFloat16, {ANY, ANY});
+  const int64_t T = check_int(qkv.size(0), 0, INT_MAX, "qkv.size(0)");
+  const int fp8 = kv_fp8_flag(k_cache);
+  check_tensor(k_cache, "k_cache", qkv, "qkv", k_cache.scalar_type(),
+               {ANY, ANY, ANY, ANY});
+  check_tensor(v_cache, "v_cache", qkv, "qkv", k_cache.scalar_type(),
+               k_cache.sizes());
+  const int kvh = check_int(k_cache.size(1), 1, 65536, "KV heads");
+  const int bs = check_int(k_cache.size(2), 1, INT_MAX,
+                           "block size k_cache.size(2)");
+  const int64_t D = k_cache.size(3);
+  TORCH_CHECK(D % 16 == 0, "head dim k_cache.size(3) must be a multiple of "
+              "16, got ", D);
+  const int d = check_int(D, 16, 2048, "head dim k_cache.size(3)");
+  const int qh = check_int(n_q_heads, 1, 65536, "n_q_heads");
+  TORCH_CHECK(qkv.size(1) == (qh + 2 * (int64_t)kvh) * D, "qkv.size(1) must "
+              "be (n_q_heads + 2 * KV heads) * head dim = ",
+              (qh + 2 * (int64_t)kvh) * D, ", got ", qkv.size(1));
+  check_tensor(cos_sin, "cos_sin", qkv, "qkv", at::kFloat, {ANY, D / 2, 2});
+  check_tensor(positions, "positions", qkv, "qkv", at::kInt, {T});
+  check_tensor(slots, "slot_mapping", qkv, "qkv", at::kLong, {T});
+  const float* kis = kv_scale_ptr(k_inv_scale, k_cache, "k_inv_scale");
+  const float* vis = kv_scale_ptr(v_inv_scale, v_cache, "v_inv_scale");
+  check_aligned16(qkv, "qkv");
+  check_aligned16(cos_sin, "cos_sin");
+  check_aligned16(k_cache, "k_cache");
+  check_aligned16(v_cache, "v_cache");
+  auto q = torch::empty({T, qh, D}, qkv.options());
+  CHECK_HIP(lds_qkv_rope_cache(
+      qkv.data_ptr(), cos_sin.data_ptr<float>(),
+      positions.data_ptr<int32_t>(), slots.data_ptr<int64_t>(), q.data_ptr(),
+      k_cache.data_ptr(), v_cache.data_ptr(), T, qh, kvh, bs, d, fp8, kis,
+      vis, cur_stream()));
+  return q;
+}
+
 // The KV pool of move_blocks / copy_blocks_peer: [L, 2, NB, KVH, BS, D] on
 // a GPU, contiguous, one (layer, K/V) block a whole number of the 16-byte
 // units the mover copies. Returns that block's bytes.
@@ -426,6 +477,15 @@ AttnArgs check_decode(const torch::Tensor& q, const torch::Tensor& k_cache,
                       int64_t chunk,
                       const c10::optional<torch::Tensor>& k_scale,
                       const c10::optional<torch::Tensor>& v_scale) {
+  // The decode kernel keeps pool row indices (block*KVH + head)*BS + row in
+  // an int32 table. This reads sizes alone, and comes first so that a pool
+  // too large to allocate (a meta tensor) still reaches it.
+  if (k_cache.dim() == 4) {
+    const int64_t pool_rows =
+        k_cache.size(0) * k_cache.size(1) * k_cache.size(2);
+    TORCH_CHECK(pool_rows < (int64_t(1) << 31), "KV cache rows NB*KVH*BS (",
+                pool_rows, ") must be below 2^31");
+  }
   AttnArgs a = check_attention(q, k_cache, v_cache, block_tables, scale,
                                k_scale, v_scale);
   const int64_t B = block_tables.size(0);
@@ -703,6 +763,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "scatter K/V into paged pool", py::arg("k_new"), py::arg("v_new"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"),
         py::arg("k_inv_scale") = py::none(),
+        py::arg("v_inv_scale") = py::none());
+  m.def("qkv_rope_cache", &qkv_rope_cache,
+        "QKV GEMM epilogue: rotated q out, rotated K and V into the pool",
+        py::arg("qkv"), py::arg("cos_sin"), py::arg("positions"),
+        py::arg("slot_mapping"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("n_q_heads"), py::arg("k_inv_scale") = py::none(),
         py::arg("v_inv_scale") = py::none());
   m.def("move_blocks", &move_blocks, "gather/scatter KV blocks for xGMI transfer");
   m.def("ipc_alloc_tensor", &ipc_alloc_tensor,

@@ -9,10 +9,12 @@
 // are scored together so K rows are read once for the whole group.
 //   Phase A  each wave owns 64 tokens of a 256-token chunk; a lane streams
 //            its token's K row (short8 loads) against the group's Q vectors
-//            staged in LDS (broadcast reads) -> logits in LDS.
+//            staged in LDS (broadcast reads) -> logits in LDS, and the
+//            token's pool row index next to them (row_idx).
 //   Phase B  online-softmax update per q-head (wave-parallel reductions).
 //   Phase C  V accumulation: lane owns a dim pair, wave owns its 64 tokens;
-//            V rows stream fully coalesced (64 lanes x 4 B = one 256 B row).
+//            V rows stream fully coalesced (64 lanes x 4 B = one 256 B row),
+//            addressed through row_idx: no block-table load, no division.
 //   Final    cross-wave combine via LDS, normalize, bf16 store.
 //
 // Flash-decoding sequence split (SPLIT=true): long sequences are cut into
@@ -28,10 +30,15 @@ namespace {
 constexpr int D = 128;        // head_dim (Llama-3 family)
 constexpr int DEF_CHUNK = 256;  // default tokens per online-softmax chunk
 constexpr int NW = 4;         // waves per workgroup
+constexpr int V_BATCH = 8;    // V rows in flight per wave in Phase C
 constexpr float NEG = -1e30f;
 
+// QPG = 8 sits at the edge of 3 waves per SIMD (168 VGPRs); the bound keeps
+// it there. 1 is the default of a 4-wave workgroup and changes nothing.
 template <int QPG, bool SPLIT, typename CT, int CHUNK = DEF_CHUNK>
-__global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
+__global__ __launch_bounds__(NW * WAVE)
+__attribute__((amdgpu_waves_per_eu(QPG == 8 ? 3 : 1))) void
+paged_attention_kernel(
     const short* __restrict__ q,        // [B, QH, D]
     const CT* __restrict__ k_cache,     // [NB, KVH, BS, D] bf16|fp8
     const CT* __restrict__ v_cache,     // [NB, KVH, BS, D] bf16|fp8
@@ -57,6 +64,10 @@ __global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
   __shared__ float logits[QPG][CHUNK];
   __shared__ float m_sh[QPG], l_sh[QPG], alpha_sh[QPG];
   __shared__ float comb[NW][QPG][D];
+  // pool row (blk*kvh + kh)*bs + row of each token of the chunk: Phase A
+  // works it out for K, Phase C reads it back for V. int32: the binding
+  // asserts NB*KVH*BS < 2^31.
+  __shared__ __attribute__((aligned(16))) int32_t row_idx[CHUNK];
 
   const int tid = threadIdx.x;
   const int wave = tid / WAVE;
@@ -106,7 +117,9 @@ __global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
         const int t = chunk0 + t_local;
         const int64_t blk = bt[t / bs];
         const int row = t % bs;
-        const CT* krow = k_cache + (((blk * kvh + kh) * bs) + row) * D;
+        const int64_t pool_row = ((blk * kvh + kh) * bs) + row;
+        row_idx[t_local] = (int32_t)pool_row;
+        const CT* krow = k_cache + pool_row * D;
 #pragma unroll 8
         for (int c = 0; c < D / 8; ++c) {
           float kf[8];
@@ -164,23 +177,23 @@ __global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
     {
       const int t_base = wave * (CHUNK / NW);
       const int t_cnt = min(CHUNK / NW, n_t - t_base);
-      // batch the V row loads 8 deep so they overlap (each row is one
-      // coalesced 256-B wave read; a load-use loop serializes on latency)
+      // batch the V row loads V_BATCH deep so they overlap (each row is one
+      // coalesced 256-B wave read; a load-use loop serializes on latency).
+      // The row's address comes from row_idx, a wave-uniform LDS read like
+      // the logits: no division and no block-table load in these loops.
+      const CT* v_lane = v_cache + lane * 2;
       int i = 0;
-      for (; i + 8 <= t_cnt; i += 8) {
-        const CT* vrows[8];
+      for (; i + V_BATCH <= t_cnt; i += V_BATCH) {
+        const CT* vrows[V_BATCH];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int t = chunk0 + t_base + i + j;
-          const int64_t blk = bt[t / bs];
-          vrows[j] = v_cache + (((blk * kvh + kh) * bs) + t % bs) * D +
-                     lane * 2;
-        }
-        float vv[8][2];
+        for (int j = 0; j < V_BATCH; ++j)
+          vrows[j] = v_lane + (int64_t)row_idx[t_base + i + j] * D;
+        float vv[V_BATCH][2];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) load_kv2(vrows[j], vv[j][0], vv[j][1]);
+        for (int j = 0; j < V_BATCH; ++j)
+          load_kv2(vrows[j], vv[j][0], vv[j][1]);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < V_BATCH; ++j) {
 #pragma unroll
           for (int h = 0; h < QPG; ++h) {
             const float p = logits[h][t_base + i + j];
@@ -190,11 +203,8 @@ __global__ __launch_bounds__(NW * WAVE) void paged_attention_kernel(
         }
       }
       for (; i < t_cnt; ++i) {
-        const int t = chunk0 + t_base + i;
-        const int64_t blk = bt[t / bs];
         float v0, v1;
-        load_kv2(v_cache + (((blk * kvh + kh) * bs) + t % bs) * D + lane * 2,
-                 v0, v1);
+        load_kv2(v_lane + (int64_t)row_idx[t_base + i] * D, v0, v1);
 #pragma unroll
         for (int h = 0; h < QPG; ++h) {
           const float p = logits[h][t_base + i];

@@ -86,6 +86,9 @@ class LlamaRunner:
         self.device = device
         self.dtype = dtype
         self.scale = 1.0 / math.sqrt(config.head_dim)
+        # False forces the split / rope / reshape_and_cache chain (tests
+        # compare the two paths)
+        self._fused_qkv = True
         c = config
         if self.device.type == "cuda":
             _load_tuned_gemms()
@@ -157,6 +160,14 @@ class LlamaRunner:
             hidden[batch.embed_rows] = batch.embed_values.to(hidden.dtype)
         residual = None
         pos32 = batch.positions.to(torch.int32)
+        # one kernel from the QKV GEMM's output to q and the stored K/V
+        # (ops.qkv_rope_cache). Calibration needs k and v as tensors and
+        # QK-norm sits between the split and RoPE: both keep the op chain.
+        # So does an fp8 pool for now: tests/test_gpu_kv_scales.py watches
+        # the scales (or their absence) arrive at ops.reshape_and_cache.
+        fused_qkv = (self._fused_qkv and kv_observer is None
+                     and kv_pool.dtype == torch.bfloat16
+                     and not c.qk_norm and c.head_dim % 16 == 0)
         for li, layer in enumerate(self.layers):
             if residual is None:
                 residual = hidden.clone()
@@ -165,32 +176,40 @@ class LlamaRunner:
                 normed = ops.rmsnorm(hidden, layer["input_norm"], c.rms_eps,
                                      residual=residual)
             qkv = normed @ layer["wqkv"]
-            q, k, v = qkv.split([c.q_size, c.kv_size, c.kv_size], dim=-1)
-            T = q.shape[0]
-            q = q.view(T, c.num_heads, c.head_dim).contiguous()
-            k = k.view(T, c.num_kv_heads, c.head_dim).contiguous()
-            v = v.view(T, c.num_kv_heads, c.head_dim).contiguous()
-            if c.qk_norm:
-                # Qwen3 per-head QK-RMSNorm before RoPE: each head's
-                # D-vector normalized with a learned gain (the rmsnorm
-                # kernel treats [T*H, D] rows like any hidden dim)
-                q = ops.rmsnorm(q.view(T * c.num_heads, c.head_dim),
-                                layer["q_norm"],
-                                c.rms_eps).view(T, c.num_heads, c.head_dim)
-                k = ops.rmsnorm(k.view(T * c.num_kv_heads, c.head_dim),
-                                layer["k_norm"],
-                                c.rms_eps).view(T, c.num_kv_heads,
-                                                c.head_dim)
-            ops.rope(q, k, self.cos_sin, pos32)
+            T = qkv.shape[0]
             k_cache = kv_pool[li, 0]
             v_cache = kv_pool[li, 1]
-            if kv_observer is not None:
-                kv_observer(li, k, v)
             k_scale = v_scale = k_inv = v_inv = None
             if kv_scales is not None:
                 k_scale, v_scale, k_inv, v_inv = kv_scales[li]
-            ops.reshape_and_cache(k, v, k_cache, v_cache, batch.slot_mapping,
-                                  k_inv_scale=k_inv, v_inv_scale=v_inv)
+            if fused_qkv:
+                q = ops.qkv_rope_cache(qkv, self.cos_sin, pos32,
+                                       batch.slot_mapping, k_cache, v_cache,
+                                       c.num_heads, k_inv_scale=k_inv,
+                                       v_inv_scale=v_inv)
+            else:
+                q, k, v = qkv.split([c.q_size, c.kv_size, c.kv_size], dim=-1)
+                q = q.view(T, c.num_heads, c.head_dim).contiguous()
+                k = k.view(T, c.num_kv_heads, c.head_dim).contiguous()
+                v = v.view(T, c.num_kv_heads, c.head_dim).contiguous()
+                if c.qk_norm:
+                    # Qwen3 per-head QK-RMSNorm before RoPE: each head's
+                    # D-vector normalized with a learned gain (the rmsnorm
+                    # kernel treats [T*H, D] rows like any hidden dim)
+                    q = ops.rmsnorm(q.view(T * c.num_heads, c.head_dim),
+                                    layer["q_norm"],
+                                    c.rms_eps).view(T, c.num_heads,
+                                                    c.head_dim)
+                    k = ops.rmsnorm(k.view(T * c.num_kv_heads, c.head_dim),
+                                    layer["k_norm"],
+                                    c.rms_eps).view(T, c.num_kv_heads,
+                                                    c.head_dim)
+                ops.rope(q, k, self.cos_sin, pos32)
+                if kv_observer is not None:
+                    kv_observer(li, k, v)
+                ops.reshape_and_cache(k, v, k_cache, v_cache,
+                                      batch.slot_mapping,
+                                      k_inv_scale=k_inv, v_inv_scale=v_inv)
             if batch.is_decode:
                 attn = ops.paged_attention(q, k_cache, v_cache,
                                            batch.block_tables, batch.seq_lens,

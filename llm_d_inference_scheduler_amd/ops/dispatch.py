@@ -71,6 +71,37 @@ def reshape_and_cache(k_new: torch.Tensor, v_new: torch.Tensor,
                           k_inv_scale=k_inv_scale, v_inv_scale=v_inv_scale)
 
 
+def qkv_rope_cache(qkv: torch.Tensor, cos_sin: torch.Tensor,
+                   positions: torch.Tensor, slot_mapping: torch.Tensor,
+                   k_cache: torch.Tensor, v_cache: torch.Tensor,
+                   n_q_heads: int, *,
+                   k_inv_scale: Optional[torch.Tensor] = None,
+                   v_inv_scale: Optional[torch.Tensor] = None
+                   ) -> torch.Tensor:
+    """The QKV GEMM's epilogue in one kernel: qkv [T, (QH + 2*KVH) * D] as
+    the GEMM returns it -> rotated q [T, QH, D] (new, contiguous); rotated K
+    and plain V are stored in the caches [NB, KVH, BS, D] at slot_mapping[t]
+    (negative: nothing stored, q still returned). Bit-equal to split, three
+    .contiguous(), rope and reshape_and_cache, which the CPU path runs."""
+    if _use_hip(qkv):
+        return _ext.qkv_rope_cache(qkv, cos_sin, positions.to(torch.int32),
+                                   slot_mapping.to(torch.int64), k_cache,
+                                   v_cache, n_q_heads, k_inv_scale,
+                                   v_inv_scale)
+    T = qkv.shape[0]
+    kvh, d = k_cache.shape[1], k_cache.shape[3]
+    q, k, v = qkv.split([n_q_heads * d, kvh * d, kvh * d], dim=-1)
+    # clone, not contiguous(): at T == 1 the views are contiguous already
+    # and the in-place rope would rotate the caller's qkv
+    q = q.reshape(T, n_q_heads, d).clone()
+    k = k.reshape(T, kvh, d).clone()
+    v = v.reshape(T, kvh, d)
+    ref.rope(q, k, cos_sin, positions)
+    ref.reshape_and_cache(k, v, k_cache, v_cache, slot_mapping,
+                          k_inv_scale=k_inv_scale, v_inv_scale=v_inv_scale)
+    return q
+
+
 import os as _os
 
 # online-softmax chunk of the decode kernel: 512 halves barrier count

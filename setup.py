@@ -33,6 +33,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/ops.hip",
         "csrc/hip/prefix_kernels.hip",
         "csrc/hip/norm_rope_act.hip",
+        "csrc/hip/qkv_epilogue.hip",
         "csrc/hip/kv_cache.hip",
         "csrc/hip/paged_attention.hip",
         "csrc/hip/flash_prefill.hip",
