@@ -114,6 +114,38 @@ hipError_t lds_flash_prefill(const AttnArgs& a, hipStream_t stream);
 // glds ring kernel: bf16 KV, max_blocks <= FLASH_GLDS_BT_CAP
 hipError_t lds_flash_prefill_glds(const AttnArgs& a, hipStream_t stream);
 
+// ---- lora.hip ------------------------------------------------------------
+
+// Columns of `in` one shrink workgroup sums: the K split count is a function
+// of `in` alone, so a row's bits do not depend on what else is launched.
+constexpr int LORA_KCHUNK = 1024;
+// Columns of `out` one expand workgroup owns.
+constexpr int LORA_NBLOCK = 256;
+
+inline int lora_k_splits(int in) { return (in + LORA_KCHUNK - 1) / LORA_KCHUNK; }
+
+// y[perm rows] += (x[perm rows] · A[slot]ᵀ) · B[slot]ᵀ, one slot per tile.
+// The caller guarantees, and nothing clamps: perm entries distinct and in
+// [0, T); per tile 1 <= count <= 16, start + count <= len(perm), slot in
+// [0, S).
+struct LoraArgs {
+  const void* x;          // [T, in] bf16, in % 32 == 0
+  void* y;                // [T, out] bf16, out % 16 == 0, updated in place
+  const void* A;          // [S, R, in] bf16
+  const void* B;          // [S, out, R] bf16, alpha / rank folded in
+  const int32_t* perm;    // adapter rows, grouped by slot
+  const int32_t* tiles;   // [n_tiles, 3] start in perm, count, slot
+  float* part;            // [lora_k_splits(in), n_tiles * 16, R] fp32 scratch
+  int n_tiles;
+  int in, out;
+  int R;                  // 16, 32, 48 or 64
+};
+
+// part = x[perm rows] · A[slot]ᵀ, one fp32 partial per K split
+hipError_t lds_lora_shrink(const LoraArgs& a, hipStream_t stream);
+// y[perm rows] += bf16(sum of partials) · B[slot]ᵀ
+hipError_t lds_lora_expand(const LoraArgs& a, hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

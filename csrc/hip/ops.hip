@@ -571,6 +571,61 @@ torch::Tensor flash_prefill(torch::Tensor q, torch::Tensor k_cache,
   return out;
 }
 
+// ---- LoRA ----
+
+// y[perm rows] += (x[perm rows] · A[slot]ᵀ) · B[slot]ᵀ in place, the slot
+// taken from the row's tile (DEVELOPMENT.md "LoRA adapters"). perm: the
+// adapter rows grouped by slot; tiles [n, 3]: (start in perm, count <= 16,
+// slot). The entries of perm and tiles are the caller's to get right
+// (ops.lora_worklist does): they are device data and checking them would
+// cost a sync.
+void lora_add(torch::Tensor y, torch::Tensor x, torch::Tensor A,
+              torch::Tensor B, torch::Tensor perm, torch::Tensor tiles) {
+  check_tensor(x, "x", x, "x", at::kBFloat16, {ANY, ANY});
+  const int64_t T = x.size(0);
+  check_int(T, 0, INT_MAX, "x.size(0)");
+  TORCH_CHECK(x.size(1) % 32 == 0, "x.size(1) must be a multiple of 32, got ",
+              x.size(1));
+  check_tensor(y, "y", x, "x", at::kBFloat16, {T, ANY});
+  TORCH_CHECK(y.size(1) % 16 == 0, "y.size(1) must be a multiple of 16, got ",
+              y.size(1));
+  check_tensor(A, "A", x, "x", at::kBFloat16, {ANY, ANY, x.size(1)});
+  const int64_t S = A.size(0), R = A.size(1);
+  TORCH_CHECK(S >= 1, "A must hold at least one slot");
+  TORCH_CHECK(R % 16 == 0 && R >= 16 && R <= 64, "the pool rank A.size(1) "
+              "must be a multiple of 16 in 16..64, got ", R);
+  check_tensor(B, "B", x, "x", at::kBFloat16, {S, y.size(1), R});
+  check_tensor(perm, "perm", x, "x", at::kInt, {ANY});
+  TORCH_CHECK(perm.size(0) <= T, "perm (", perm.size(0), ") must not be "
+              "longer than x has rows (", T, ")");
+  check_tensor(tiles, "tiles", x, "x", at::kInt, {ANY, 3});
+  check_aligned16(x, "x");
+  check_aligned16(y, "y");
+  check_aligned16(A, "A");
+  check_aligned16(B, "B");
+  LoraArgs a{};
+  a.in = check_int(x.size(1), 0, INT_MAX, "x.size(1)");
+  a.out = check_int(y.size(1), 0, GRID_YZ_MAX * (int64_t)LORA_NBLOCK,
+                    "y.size(1)");
+  a.R = (int)R;
+  a.n_tiles = check_int(tiles.size(0), 0, INT_MAX / (16 * 64),
+                        "tiles.size(0)");
+  if (a.n_tiles == 0 || a.in == 0 || a.out == 0) return;
+  const int n_split = check_int(lora_k_splits(a.in), 1, GRID_YZ_MAX,
+                                "K splits of x.size(1)");
+  auto part = torch::empty({n_split, (int64_t)a.n_tiles * 16, R},
+                           x.options().dtype(torch::kFloat32));
+  a.x = x.data_ptr();
+  a.y = y.data_ptr();
+  a.A = A.data_ptr();
+  a.B = B.data_ptr();
+  a.perm = perm.data_ptr<int32_t>();
+  a.tiles = tiles.data_ptr<int32_t>();
+  a.part = part.data_ptr<float>();
+  CHECK_HIP(lds_lora_shrink(a, cur_stream()));
+  CHECK_HIP(lds_lora_expand(a, cur_stream()));
+}
+
 // ---- sampler ----
 
 // One per-row parameter vector of sample(): [B], on the logits' device.
@@ -795,6 +850,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_tables"), py::arg("seq_meta"), py::arg("tiles"),
         py::arg("scale"), py::arg("k_scale") = py::none(),
         py::arg("v_scale") = py::none());
+  m.def("lora_add", &lora_add,
+        "batched multi-adapter LoRA: y[perm rows] += (x A[slot]^T) B[slot]^T",
+        py::arg("y"), py::arg("x"), py::arg("A"), py::arg("B"),
+        py::arg("perm"), py::arg("tiles"));
   m.def("sample", &sample,
         "fused temperature/top-k/top-p/seeded sampler with logprobs -> "
         "(tokens, logprobs, n_kept, threshold)",

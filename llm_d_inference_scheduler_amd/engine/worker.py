@@ -24,9 +24,10 @@ import torch
 from .. import ops
 from ..datalayer.endpoint import Metrics, Role
 from ..models.configs import ModelConfig
-from ..models.llama import ForwardBatch, LlamaRunner
+from ..models.llama import ForwardBatch, LlamaRunner, LoraBatch
 from ..utils.logging import get_logger
 from .kvcache import BLOCK_SIZE, BlockManager, KVPool, block_hashes
+from .lora import LoraAdapter, LoraSlots, adapter_hash_seed
 
 log = get_logger("engine.worker")
 
@@ -58,6 +59,8 @@ class EngineRequest:
     frequency_penalty: float = 0.0      # 0 = off
     min_p: float = 0.0                  # 0 = off
     top_logprobs: int = 0               # alternatives per token, 0..20
+    # name of a registered LoRA adapter, "" = the base model
+    adapter: str = ""
     # runtime state
     computed: int = 0               # prompt tokens already prefilled
     generated: List[int] = field(default_factory=list)
@@ -188,6 +191,11 @@ class DecodeState:
         self.top_n = None
         self.state_row = None
         self.ext_rows: set = set()
+        # LoRA slot per row (host side), -1 = none; the work list of the
+        # active rows is cached like rows_for's tensor
+        self.lora_slot: List[int] = []
+        self._lora_ids: Optional[List[str]] = None
+        self._lora_batch: Optional[LoraBatch] = None
         self.free_rows: List[int] = []
         self.row_of: Dict[str, int] = {}
         self._active_ids: List[str] = []
@@ -229,6 +237,7 @@ class DecodeState:
         self.bt, self.seq_lens, self.last_tok, self.temps = bt, sl, lt, tp
         self.top_k, self.top_p, self.seed, self.pos_off = tk, pp, sd, po
         self.free_rows.extend(range(new_cap - 1, old - 1, -1))
+        self.lora_slot.extend([-1] * (new_cap - old))
         self.capacity = new_cap
 
     def take_row(self) -> int:
@@ -237,9 +246,13 @@ class DecodeState:
         return self.free_rows.pop()
 
     def join(self, req: EngineRequest, table: List[int], seq_len: int,
-             last_token: int, state_row: int = -1) -> None:
-        """state_row: the request's row of the token-state pool, -1 = none."""
+             last_token: int, state_row: int = -1,
+             lora_slot: int = -1) -> None:
+        """state_row: the request's row of the token-state pool, -1 = none.
+        lora_slot: the slot its adapter is resident in, -1 = base model."""
         row = self.take_row()
+        self.lora_slot[row] = lora_slot
+        self._lora_ids = None
         if req.uses_ext:
             self.rep[row] = req.repetition_penalty
             self.pres[row] = req.presence_penalty
@@ -285,6 +298,7 @@ class DecodeState:
             self.free_rows.append(row)
             self._active_ids = []
             self._rows_t = None
+            self._lora_ids = None
 
     def rows_for(self, ids: List[str]) -> torch.Tensor:
         if ids != self._active_ids:
@@ -293,6 +307,21 @@ class DecodeState:
                 device=self.device)
             self._active_ids = list(ids)
         return self._rows_t
+
+    def lora_for(self, ids: List[str]) -> Optional[LoraBatch]:
+        """The LoRA work list of a decode batch over `ids`, in batch order;
+        None when no row has an adapter. Rebuilt (one small H2D copy) only
+        when membership changed since the last call."""
+        if ids != self._lora_ids:
+            row_slot = [self.lora_slot[self.row_of[i]] for i in ids]
+            self._lora_batch = None
+            if any(s >= 0 for s in row_slot):
+                perm, tiles = ops.lora_worklist(row_slot)
+                self._lora_batch = LoraBatch(
+                    perm.to(self.device, non_blocking=True),
+                    tiles.to(self.device, non_blocking=True))
+            self._lora_ids = list(ids)
+        return self._lora_batch
 
 
 class TokenStatePool:
@@ -378,7 +407,9 @@ class EngineWorker:
                  seed: int = 0,
                  kv_scales: str = "none",
                  kv_scale_headroom: float = 2.0,
-                 kv_calib_tokens: int = 2048):
+                 kv_calib_tokens: int = 2048,
+                 max_loras: int = 0,
+                 max_lora_rank: int = 16):
         """kv_scales selects the per-head scales of an fp8 KV cache
         (KVPool): "none" (unscaled direct cast), "calibrate" (run
         calibrate_kv_scales() at start-up) or the path of a scales JSON
@@ -387,7 +418,12 @@ class EngineWorker:
         far off they are has not been measured, so a deployment with a
         calibrated checkpoint should pass its scales file. Where fp8 falls
         back to the compute dtype (non-GPU devices) kv_scales is accepted
-        and ignored, and pool.scales stays None."""
+        and ignored, and pool.scales stays None.
+
+        max_loras adapters can be resident at once, in slot pools of rank
+        max_lora_rank rounded up to a multiple of 16 (DEVELOPMENT.md "LoRA
+        adapters"); with max_loras=0 nothing is allocated and no request may
+        name an adapter."""
         self.cfg = config
         self.device = torch.device(device)
         self._is_cuda_dev = lambda: self.device.type == "cuda"
@@ -415,6 +451,17 @@ class EngineWorker:
                                 prefix_caching=prefix_caching)
         self.model = LlamaRunner(config, self.device, dtype, seed=seed)
         self.seed = seed
+        self.max_loras = max_loras
+        self.adapters: Dict[str, LoraAdapter] = {}   # registered, on the host
+        self._adapter_tensors: Dict[str, list] = {}  # as a slot holds them
+        # request id -> adapter of a KV hand-off on its way here: its slot is
+        # held from reserve_lora_slot until admit_transferred or abort
+        self._lora_pins: Dict[str, str] = {}
+        self.lora: Optional[LoraSlots] = None
+        if max_loras > 0:
+            self.lora = LoraSlots(config, max_loras,
+                                  -(-max_lora_rank // 16) * 16, self.device,
+                                  dtype)
         self._admitted = 0      # admission counter (derived sampler seeds)
         self.kv_scale_headroom = kv_scale_headroom
         self.kv_calib_tokens = kv_calib_tokens
@@ -543,6 +590,95 @@ class EngineWorker:
         self._invalidate_cached_kv()
         return amax[:, 0], amax[:, 1]
 
+    # ---- LoRA adapters -------------------------------------------------
+    def _adapter_users(self) -> List[str]:
+        """Adapters a slot reload would pull from under: those of running
+        requests (a pending decode step's requests are among them) and of
+        waiting requests whose prefill has begun."""
+        return [r.adapter for r in self.running if r.adapter] + \
+               [r.adapter for r in self.waiting
+                if r.adapter and r.request_id in self.mgr.tables] + \
+               list(self._lora_pins.values())
+
+    def reserve_lora_slot(self, request_id: str, adapter: str) -> bool:
+        """Make `adapter` resident for a request that will arrive through
+        admit_transferred, and hold its slot until then (or until abort /
+        release_lora_slot). False when the adapter is not registered or every
+        slot is in use by others; nothing is held then. True for ""."""
+        if not adapter:
+            return True
+        if adapter not in self.adapters or \
+                self._lora_slot_for(adapter) is None:
+            return False
+        self._lora_pins[request_id] = adapter
+        return True
+
+    def release_lora_slot(self, request_id: str) -> None:
+        self._lora_pins.pop(request_id, None)
+
+    def register_adapter(self, adapter: LoraAdapter) -> None:
+        """Make `adapter` servable under its name. It stays on the host,
+        padded and folded as a slot holds it, until a request needs it.
+        Other content under a registered name raises: the prefix-cache seed
+        is the name, so a silent swap would hand the new adapter KV computed
+        under the old one. Unregister first."""
+        if self.lora is None:
+            raise RuntimeError("this worker was built with max_loras=0")
+        old = self.adapters.get(adapter.name)
+        if old is not None:
+            if old.content_id != adapter.content_id:
+                raise ValueError(f"adapter {adapter.name} is registered with "
+                                 "other content; unregister it first")
+            return
+        self._adapter_tensors[adapter.name] = self.lora.host_tensors(adapter)
+        self.adapters[adapter.name] = adapter
+
+    def unregister_adapter(self, name: str) -> None:
+        """Forget `name`. Cached KV is forgotten with it (all of it: blocks
+        do not record their adapter), so a later adapter of that name never
+        matches blocks computed under this one."""
+        if any(r.adapter == name for r in self._by_id.values()):
+            raise RuntimeError(f"adapter {name} is in use")
+        if self.adapters.pop(name, None) is not None:
+            self._adapter_tensors.pop(name, None)
+            self.lora.drop(name)
+            self._invalidate_cached_kv()
+
+    def _lora_slot(self, req: EngineRequest) -> int:
+        """The slot `req`'s adapter is resident in, loading it if need be;
+        -1 for a base request, None when every slot is in use by others."""
+        return self._lora_slot_for(req.adapter)
+
+    def _lora_slot_for(self, adapter: str) -> int:
+        if not adapter:
+            return -1
+        ls = self.lora
+        if adapter in ls.slot_of:
+            return ls.touch(adapter)
+        slot = ls.victim(self._adapter_users())
+        if slot is None:
+            return None
+        # The copy runs on the current stream. With the overlap on, kernels
+        # of the other stream may still read the slot's old content and will
+        # read the new: order the copy against both.
+        other = None
+        if self._cuda and self._prefill_stream is not None:
+            cur = torch.cuda.current_stream(self.device)
+            other = self._prefill_stream
+            if cur == other:
+                other = torch.cuda.default_stream(self.device)
+            cur.wait_stream(other)
+        ls.load(slot, adapter, self._adapter_tensors[adapter])
+        if other is not None:
+            other.wait_stream(torch.cuda.current_stream(self.device))
+        return slot
+
+    def _hash_prompt(self, req: EngineRequest) -> None:
+        if req.block_hashes is None:
+            req.block_hashes = block_hashes(
+                req.prompt_tokens, self.pool.block_size,
+                adapter_hash_seed(req.adapter))
+
     # ------------------------------------------------------------------
     def _reject(self, req: EngineRequest, error: str) -> None:
         self._rejects.append(RequestOutput(
@@ -555,6 +691,9 @@ class EngineWorker:
             # an empty prompt would be silently dropped in _prefill_pass
             # (remaining <= 0) and the client would hang until timeout
             self._reject(req, "empty_prompt: prompt tokenized to 0 tokens")
+            return
+        if req.adapter and req.adapter not in self.adapters:
+            self._reject(req, f"adapter_not_found: {req.adapter}")
             return
         if len(req.prompt_tokens) >= self.max_model_len:
             # reject, never truncate: a silently-truncated prompt produces
@@ -619,10 +758,16 @@ class EngineWorker:
         for a logprobs=True request, first_top_logprobs its top-N list. A
         penalised request's token state is rebuilt here from the prompt and
         the first token, which counts as output."""
+        if req.adapter and req.adapter not in self.adapters:
+            raise RuntimeError(f"adapter_not_found: {req.adapter}")
+        # a caller that moves KV here reserves the slot first
+        # (reserve_lora_slot), so this finds the adapter resident
+        lora_slot = self._lora_slot(req)
+        if lora_slot is None:
+            raise RuntimeError("no LoRA slot free for a transferred request: "
+                               "reserve_lora_slot() before the transfer")
         self.mgr.adopt(req.request_id, local_blocks, seq_len)
-        if req.block_hashes is None:
-            req.block_hashes = block_hashes(req.prompt_tokens,
-                                            self.pool.block_size)
+        self._hash_prompt(req)
         full = min(len(local_blocks), req.prompt_len // self.pool.block_size)
         for b in range(full):
             self.mgr.register_block(req.request_id, b,
@@ -642,11 +787,14 @@ class EngineWorker:
             req.slo_ok = False
         self._by_id[req.request_id] = req
         self.running.append(req)
+        self._lora_pins.pop(req.request_id, None)   # running holds it now
         self.tstate.fill([req])
         self.dstate.join(req, local_blocks, seq_len, first_token,
-                         self.tstate.row_of.get(req.request_id, -1))
+                         self.tstate.row_of.get(req.request_id, -1),
+                         lora_slot)
 
     def abort(self, request_id: str) -> None:
+        self._lora_pins.pop(request_id, None)
         req = self._by_id.pop(request_id, None)
         if req is None:
             return
@@ -660,12 +808,21 @@ class EngineWorker:
 
     # ------------------------------------------------------------------
     def metrics_snapshot(self) -> Metrics:
+        def by_adapter(reqs):
+            counts: Dict[str, int] = {}
+            for r in reqs:
+                if r.adapter:
+                    counts[r.adapter] = counts.get(r.adapter, 0) + 1
+            return counts
         return Metrics(
             waiting_queue_size=len(self.waiting),
             running_requests_size=len(self.running),
             kv_cache_usage=self.mgr.usage,
             cache_block_size=self.pool.block_size,
             cache_num_blocks=self.pool.num_blocks,
+            active_models=by_adapter(self.running),
+            waiting_models=by_adapter(self.waiting),
+            max_active_models=self.max_loras,
         )
 
     @property
@@ -736,9 +893,7 @@ class EngineWorker:
     # ---- prefill ----
     def _admit_prompt(self, req: EngineRequest) -> None:
         """First touch: match + reuse cached prefix blocks (engine APC)."""
-        if req.block_hashes is None:
-            req.block_hashes = block_hashes(req.prompt_tokens,
-                                            self.pool.block_size)
+        self._hash_prompt(req)
         matched = self.mgr.allocate_prompt(req.request_id, req.block_hashes,
                                            req.prompt_len)
         req.computed = matched
@@ -748,7 +903,8 @@ class EngineWorker:
 
     def _prefill_batch(self, input_ids, positions, slots, seq_starts,
                        ctx_lens, tables, metas, logit_rows,
-                       embed_rows=(), embed_vals=()) -> ForwardBatch:
+                       embed_rows=(), embed_vals=(),
+                       row_slot=None) -> ForwardBatch:
         """The ForwardBatch of one prefill pass from host-side arrays:
         flash-prefill metadata on the GPU path, per-sequence block tables
         for the composed path otherwise."""
@@ -774,7 +930,13 @@ class EngineWorker:
         else:
             bt_list = [torch.tensor(t, dtype=torch.int32,
                                     device=self.device) for t in tables]
+        lora = None
+        if row_slot is not None:
+            perm, tiles = ops.lora_worklist(row_slot)
+            lora = LoraBatch(perm.to(self.device, non_blocking=True),
+                             tiles.to(self.device, non_blocking=True))
         batch = ForwardBatch(
+            lora=lora,
             input_ids=torch.from_numpy(input_ids).to(self.device,
                                                      non_blocking=True),
             positions=torch.from_numpy(
@@ -807,6 +969,10 @@ class EngineWorker:
             if budget <= 0:
                 break
             if req.request_id not in self.mgr.tables:
+                if self._lora_slot(req) is None:
+                    # every slot is held by requests in flight: the request
+                    # waits, later ones may pass it
+                    continue
                 self._admit_prompt(req)
             remaining = req.prompt_len - req.computed
             if remaining <= 0:
@@ -834,6 +1000,11 @@ class EngineWorker:
         finishing: List[EngineRequest] = []
         bs = self.pool.block_size
         metas = []                      # (seq_start, chunk, prior) per seq
+        row_slot = None
+        if any(req.adapter for req, _ in selected):
+            row_slot = np.concatenate([
+                np.full(chunk, self._lora_slot(req), dtype=np.int32)
+                for req, chunk in selected])
         for req, chunk in selected:
             start, end = req.computed, req.computed + chunk
             metas.append((seq_starts[-1], chunk, start))
@@ -874,11 +1045,12 @@ class EngineWorker:
 
         batch = self._prefill_batch(input_ids, positions, slots, seq_starts,
                                     ctx_lens, tables, metas, logit_rows,
-                                    embed_rows, embed_vals)
+                                    embed_rows, embed_vals, row_slot)
         embedding_reqs = [r for r in finishing if r.is_embedding]
         hidden_or_logits = self.model.forward(
             batch, self.pool.tensor, embeddings_out=bool(embedding_reqs),
-            kv_scales=self.pool.all_layer_scales())
+            kv_scales=self.pool.all_layer_scales(),
+            **self._lora_kw(batch))
 
         outputs: List[RequestOutput] = []
         now = time.time()
@@ -956,13 +1128,19 @@ class EngineWorker:
                 self.running.append(req)
                 self.dstate.join(req, self.mgr.tables[req.request_id],
                                  self.mgr.seq_lens[req.request_id], int(tok),
-                                 self.tstate.row_of.get(req.request_id, -1))
+                                 self.tstate.row_of.get(req.request_id, -1),
+                                 self._lora_slot(req))
                 outputs.append(RequestOutput(
                     request_id=req.request_id, new_tokens=[int(tok)],
                     ttft_ms=(now - req.arrival_t) * 1e3,
                     cached_tokens=req.cached_tokens, new_logprobs=new_lp,
                     new_top_logprobs=new_top))
                 self.total_generated += 1
+
+    def _lora_kw(self, batch: ForwardBatch) -> dict:
+        """forward()'s LoRA argument: absent on a batch without adapter rows,
+        so that call is today's."""
+        return {} if batch.lora is None else {"lora_weights": self.lora.pools}
 
     def release_prefilled(self, request_id: str) -> None:
         """Free a prefill-only sequence after its KV was shipped over xGMI."""
@@ -1021,7 +1199,8 @@ class EngineWorker:
                   ] = torch.tensor(upd_val, dtype=torch.int32,
                                    device=self.device)
 
-        rows_t = st.rows_for([r.request_id for r in active])
+        active_ids = [r.request_id for r in active]
+        rows_t = st.rows_for(active_ids)
         lens = st.seq_lens.index_select(0, rows_t)
         new_len = lens + 1
         pos = new_len - 1                           # int32 positions
@@ -1036,8 +1215,11 @@ class EngineWorker:
             block_tables=bt_rows, seq_lens=new_len,
             max_seq_len=max(self.mgr.seq_lens[r.request_id]
                             for r in active))
+        if self.lora is not None:
+            batch.lora = st.lora_for(active_ids)
         logits = self.model.forward(batch, self.pool.tensor,
-                                    kv_scales=self.pool.all_layer_scales())
+                                    kv_scales=self.pool.all_layer_scales(),
+                                    **self._lora_kw(batch))
         lp = top = None
         if any(r.uses_ext for r in active):
             # as below, through sample_ext: it reads each row's penalties

@@ -77,6 +77,18 @@ class ForwardBatch:
     # multimodal: rows whose input embedding is provided (encode hand-off)
     embed_rows: Optional[torch.Tensor] = None     # [n] int64 into T
     embed_values: Optional[torch.Tensor] = None   # [n, hidden]
+    # LoRA work list (ops.lora_worklist) as device tensors, or None: no row
+    # of this batch has an adapter
+    lora: Optional["LoraBatch"] = None
+
+
+@dataclass
+class LoraBatch:
+    perm: torch.Tensor               # int32, adapter rows grouped by slot
+    tiles: torch.Tensor              # [n, 3] int32 start, count, slot
+
+
+LORA_TARGETS = ("wqkv", "wo", "wgate_up", "wdown")
 
 
 class LlamaRunner:
@@ -145,7 +157,8 @@ class LlamaRunner:
     # ------------------------------------------------------------------
     def forward(self, batch: ForwardBatch, kv_pool: torch.Tensor,
                 embeddings_out: bool = False,
-                kv_scales=None, kv_observer=None) -> torch.Tensor:
+                kv_scales=None, kv_observer=None,
+                lora_weights=None) -> torch.Tensor:
         """Returns logits [n_logit_rows, vocab] (or final hidden states for
         embeddings_out). kv_pool: [L, 2, NB, KVH, BS, D].
 
@@ -153,8 +166,19 @@ class LlamaRunner:
         (KVPool.all_layer_scales(): per layer the [KVH] fp32 views k_scale,
         v_scale, k_inv_scale, v_inv_scale), None otherwise.
         kv_observer(li, k, v), if given, sees each layer's post-RoPE K and
-        its V [T, KVH, D] just before the store (calibration)."""
+        its V [T, KVH, D] just before the store (calibration).
+        lora_weights: per layer, target -> (A [S, R, in], B [S, out, R]) slot
+        pools; read only when batch.lora names rows (DEVELOPMENT.md "LoRA
+        adapters"). The update of the fused wqkv goes into qkv, ahead of
+        RoPE and the KV store."""
         c = self.cfg
+        lora = batch.lora
+        if lora is not None and lora_weights is None:
+            raise ValueError("batch.lora needs lora_weights")
+
+        def lora_add(y, x, li, target):
+            A, B = lora_weights[li][target]
+            ops.lora_add(y, x, A, B, lora.perm, lora.tiles)
         hidden = self.embed[batch.input_ids]
         if batch.embed_rows is not None and batch.embed_rows.numel():
             hidden[batch.embed_rows] = batch.embed_values.to(hidden.dtype)
@@ -176,6 +200,8 @@ class LlamaRunner:
                 normed = ops.rmsnorm(hidden, layer["input_norm"], c.rms_eps,
                                      residual=residual)
             qkv = normed @ layer["wqkv"]
+            if lora is not None:
+                lora_add(qkv, normed, li, "wqkv")
             T = qkv.shape[0]
             k_cache = kv_pool[li, 0]
             v_cache = kv_pool[li, 1]
@@ -219,12 +245,19 @@ class LlamaRunner:
             else:
                 attn = self._prefill_attention(batch, q, k_cache, v_cache,
                                                k_scale, v_scale)
-            o = attn.view(T, c.q_size) @ layer["wo"]
+            attn = attn.view(T, c.q_size)
+            o = attn @ layer["wo"]
+            if lora is not None:
+                lora_add(o, attn, li, "wo")
             normed2 = ops.rmsnorm(o, layer["post_norm"], c.rms_eps,
                                   residual=residual)
             gate_up = normed2 @ layer["wgate_up"]
+            if lora is not None:
+                lora_add(gate_up, normed2, li, "wgate_up")
             act = ops.silu_mul(gate_up)
             hidden = act @ layer["wdown"]
+            if lora is not None:
+                lora_add(hidden, act, li, "wdown")
         final = ops.rmsnorm(hidden, self.final_norm, c.rms_eps,
                             residual=residual)
         # `residual` now holds the pre-norm sum; `final` the normed states

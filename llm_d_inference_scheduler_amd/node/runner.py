@@ -23,6 +23,7 @@ import torch
 from ..config import LoadedConfig, load_config
 from ..datalayer.datastore import Datastore, make_endpoint
 from ..datalayer.endpoint import Metrics, Role
+from ..engine.lora import adapter_from_spec, adapter_hash_seed
 from ..engine.worker import EngineRequest, EngineWorker, RequestOutput
 from ..flowcontrol import (BandConfig, FlowController, FlowRegistry,
                            UtilizationSaturationDetector)
@@ -148,6 +149,13 @@ class NodeConfig:
     # head-of-line blocking and enabling mid-generation rebalancing
     decode_chunk_tokens: Optional[int] = None
     seed: int = 0
+    # LoRA (DEVELOPMENT.md "LoRA adapters"): adapters resident at once, the
+    # slot pools' rank, and name -> file path or "random:rank=..,seed=.."
+    # spec; every rank registers them at start-up. A request whose model is
+    # one of the names runs under that adapter
+    max_loras: int = 0
+    max_lora_rank: int = 16
+    lora_adapters: Dict[str, str] = field(default_factory=dict)
     mailbox_group: Any = None
     transfer_group: Any = None
 
@@ -211,7 +219,13 @@ class NodeRunner:
             overlap_streams=cfg.overlap_streams,
             seed=cfg.seed, kv_scales=cfg.kv_scales,
             kv_scale_headroom=cfg.kv_scale_headroom,
-            kv_calib_tokens=cfg.kv_calib_tokens)
+            kv_calib_tokens=cfg.kv_calib_tokens,
+            max_loras=cfg.max_loras, max_lora_rank=cfg.max_lora_rank)
+        if cfg.lora_adapters and cfg.max_loras <= 0:
+            raise ValueError("lora_adapters needs max_loras >= 1")
+        for name, spec in cfg.lora_adapters.items():
+            self.engine.register_adapter(
+                adapter_from_spec(name, spec, cfg.model))
         log.info("KV cache", dtype=str(self.engine.pool.cache_dtype),
                  kv_scales=cfg.kv_scales,
                  scales_id=self.engine.pool.scales_id or "unscaled")
@@ -237,6 +251,8 @@ class NodeRunner:
         self._pending_adoption: Dict[str, Dict[str, Any]] = {}
         # prefill-side: req_id -> decode rank for the eventual hand-off
         self._handoff_dst: Dict[str, int] = {}
+        # prefill-side: req_id -> adapter name of a hand-off under an adapter
+        self._handoff_adapter: Dict[str, str] = {}
         # shared-storage connector: prefill jobs deferred until the decode
         # side reports a cache miss (try-decode-first)
         self._deferred_prefill: Dict[str, EngineRequest] = {}
@@ -364,6 +380,9 @@ class NodeRunner:
                 self._approx = p
             elif isinstance(p, PrecisePrefixCacheScorer):
                 self._precise = p
+                # the engines hash an adapter request's blocks with the
+                # adapter's seed: the scorer must know which names are
+                p.adapter_names = set(self.engine.adapters)
 
         # endpoint lifecycle events fan out to plugin remove hooks — the
         # notification-source surface that drives the reference's precise
@@ -474,6 +493,7 @@ class NodeRunner:
         self.engine.abort(rid)
         self._deferred_prefill.pop(rid, None)
         self._handoff_dst.pop(rid, None)
+        self._handoff_adapter.pop(rid, None)
         self._streaming_ids.discard(rid)
         pend = self._pending_adoption.pop(rid, None)
         if pend and pend.get("reserved"):
@@ -668,6 +688,9 @@ class NodeRunner:
                    "arrival": float(req.headers.get("x-arrival-wall", 0) or 0),
                    "seq": self._assign_seq}
             self._assign_seq += 1
+            if req.target_model in self.engine.adapters:
+                # any other name goes to the base model
+                msg["adapter"] = req.target_model
             prefill_hdr = req.headers.get("x-prefiller-host-port")
             if prefill_hdr:
                 msg["prefill"] = int(prefill_hdr.split(":")[-1])
@@ -697,7 +720,8 @@ class NodeRunner:
         m = self.engine.metrics_snapshot()
         return {"q": m.waiting_queue_size, "r": m.running_requests_size,
                 "kv": m.kv_cache_usage, "nb": m.cache_num_blocks,
-                "bs": m.cache_block_size}
+                "bs": m.cache_block_size, "am": m.active_models,
+                "wm": m.waiting_models, "mam": m.max_active_models}
 
     def _process_messages(self, msgs: List[Dict[str, Any]]) -> None:
         for m in msgs:
@@ -710,7 +734,10 @@ class NodeRunner:
                         running_requests_size=m["m"]["r"],
                         kv_cache_usage=m["m"]["kv"],
                         cache_num_blocks=m["m"]["nb"],
-                        cache_block_size=m["m"]["bs"]))
+                        cache_block_size=m["m"]["bs"],
+                        active_models=dict(m["m"].get("am") or {}),
+                        waiting_models=dict(m["m"].get("wm") or {}),
+                        max_active_models=m["m"].get("mam", 0)))
             elif t == "assign":
                 self._handle_assign(m)
             elif t == "done" and self.is_router:
@@ -724,6 +751,7 @@ class NodeRunner:
             elif t == "pd_skip":
                 self._deferred_prefill.pop(m["req_id"], None)
                 self._handoff_dst.pop(m["req_id"], None)
+                self._handoff_adapter.pop(m["req_id"], None)
             elif t == "kv_released" and m.get("dst") == self.rank:
                 # peer-pull transport: the decode rank finished (or
                 # abandoned) its one-sided pull; the prefill blocks are
@@ -755,7 +783,8 @@ class NodeRunner:
             cached_tokens=m.get("cached", 0),
             priority=m.get("priority", 0),
             stop_token_ids=m.get("stop"),
-            arrival_t=m.get("arrival") or 0.0)
+            arrival_t=m.get("arrival") or 0.0,
+            adapter=m.get("adapter", ""))
         # the rank that runs the prompt (prefill stage or monolithic decode)
         prompt_rank = prefill_rank if (
             prefill_rank is not None and prefill_rank != decode_rank) \
@@ -767,6 +796,8 @@ class NodeRunner:
             if prompt_rank != decode_rank:
                 req.prefill_only = True
                 self._handoff_dst[m["req_id"]] = decode_rank
+                if req.adapter:
+                    self._handoff_adapter[m["req_id"]] = req.adapter
             if encode_ranks:
                 # E stage first: hold until embeddings arrive over xGMI
                 self._awaiting_embeds[m["req_id"]] = {
@@ -787,12 +818,11 @@ class NodeRunner:
                 cached_tokens=m.get("cached", 0),
                 priority=m.get("priority", 0),
                 stop_token_ids=m.get("stop"),
-                arrival_t=m.get("arrival") or 0.0)
+                arrival_t=m.get("arrival") or 0.0,
+                adapter=m.get("adapter", ""))
             local_hit = False
             if shared_storage:
-                from ..engine.kvcache import block_hashes
-                h = block_hashes(decode_req.prompt_tokens,
-                                 self.engine.pool.block_size)
+                h = self._probe_hashes(decode_req)
                 matched = self.engine.mgr.match_prefix(
                     h, len(decode_req.prompt_tokens))
                 frac = matched / max(1, len(decode_req.prompt_tokens))
@@ -823,6 +853,22 @@ class NodeRunner:
                                       "dst": prompt_rank})
         if m.get("stream") and self.rank == decode_rank:
             self._streaming_ids.add(m["req_id"])
+
+    def _probe_hashes(self, req: EngineRequest):
+        """The block hashes the shared-storage probe looks up: seeded by the
+        request's adapter as the engine's own are, so KV computed under
+        another adapter, or under none, is never a hit."""
+        from ..engine.kvcache import block_hashes
+        return block_hashes(req.prompt_tokens, self.engine.pool.block_size,
+                            adapter_hash_seed(req.adapter))
+
+    def _adapter_id(self, name: str) -> str:
+        """content_id of a registered adapter, "" for the base model, "?" for
+        a name this rank does not know (equal to no content_id)."""
+        if not name:
+            return ""
+        ad = self.engine.adapters.get(name)
+        return ad.content_id if ad is not None else "?"
 
     def _handle_done(self, m: Dict[str, Any]) -> None:
         decision = self._decisions.pop(m["req_id"], None)
@@ -974,6 +1020,23 @@ class NodeRunner:
         # scales would decode to garbage here, so refuse them
         mismatch = job.get("kv_scales_id", "") != self.engine.pool.scales_id
         pending0 = self._pending_adoption.get(req_id)
+        # ... and so would KV computed under an adapter this rank holds with
+        # other content, or not at all. The adapter is read from the pending
+        # adoption: without one (aborted meanwhile) there is no request to
+        # compare with, the blocks taken below go back in _adopt, and nothing
+        # is ever admitted.
+        refused = "kv_scale_mismatch" if mismatch else ""
+        if not mismatch and pending0 is not None:
+            adapter = pending0["req"].adapter
+            if job.get("adapter_id", "") != self._adapter_id(adapter):
+                mismatch, refused = True, "adapter_mismatch"
+            elif not self.engine.reserve_lora_slot(req_id, adapter):
+                # Every slot is held by requests in flight. A hand-off cannot
+                # wait in the engine's queue as a local request does (its
+                # blocks on the prefill rank would stay taken), so it fails
+                # cleanly, before any block is taken here; the slot of one
+                # that passes is held until admit_transferred.
+                mismatch, refused = True, "lora_slots_busy"
         reserved = (pending0 or {}).get("reserved")
         if pending0 is not None:
             # ownership of the reservation moves to this job NOW: an abort
@@ -985,18 +1048,19 @@ class NodeRunner:
             reserved = None
         if mismatch:
             local = None
-            log.warning("kv hand-off dropped: fp8 KV scales differ",
+            log.warning("kv hand-off dropped: " + refused,
                         req=req_id, src_scales=job.get("kv_scales_id", ""),
-                        dst_scales=self.engine.pool.scales_id)
+                        dst_scales=self.engine.pool.scales_id,
+                        src_adapter=job.get("adapter_id", ""))
         else:
             local = reserved if reserved is not None else \
                 self.engine.mgr.take_blocks(n)
         if local is None:
-            # cannot adopt (kv_exhausted, or foreign scales): drop the
-            # hand-off
+            # cannot adopt (kv_exhausted, foreign scales, adapter content or
+            # no slot): drop the hand-off
+            self.engine.release_lora_slot(req_id)
             self._outbox.append({"type": "done", "req_id": req_id,
-                                 "error": "kv_scale_mismatch" if mismatch
-                                 else "kv_exhausted"})
+                                 "error": refused or "kv_exhausted"})
             self._pending_adoption.pop(req_id, None)
             if peer:
                 # nothing was pulled; free the src blocks immediately
@@ -1011,6 +1075,7 @@ class NodeRunner:
             pending = self._pending_adoption.pop(req_id, None)
             if pending is None:           # aborted while in flight
                 self.engine.mgr.release_blocks(local)
+                self.engine.release_lora_slot(req_id)
             else:
                 self.engine.admit_transferred(pending["req"], local,
                                               job["seq_len"],
@@ -1074,7 +1139,9 @@ class NodeRunner:
                                            if out.new_top_logprobs
                                            else None),
                     "ttft_ms": out.ttft_ms,
-                    "kv_scales_id": self.engine.pool.scales_id})
+                    "kv_scales_id": self.engine.pool.scales_id,
+                    "adapter_id": self._adapter_id(
+                        self._handoff_adapter.pop(out.request_id, ""))})
             elif out.kind == "embedding" and out.finished:
                 self._emit_done(out, tokens=[])
             else:

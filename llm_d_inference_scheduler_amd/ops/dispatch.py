@@ -214,6 +214,25 @@ def token_state_fill(state: torch.Tensor, rows: torch.Tensor,
     ref.token_state_fill(state, rows, tokens, offsets, n_prompt, V)
 
 
+def lora_worklist(row_slot):
+    """(perm, tiles) of a batch from its per-row adapter slots, -1 for none
+    (CPU int32 tensors; ops.ref.lora_worklist)."""
+    return ref.lora_worklist(row_slot)
+
+
+def lora_add(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+             B: torch.Tensor, perm: torch.Tensor, tiles: torch.Tensor) -> None:
+    """Batched multi-adapter LoRA, in place (DEVELOPMENT.md "LoRA adapters"):
+    y[row] += (x[row] · A[slot]ᵀ) · B[slot]ᵀ for the rows listed in perm
+    (int32, grouped by slot), the slot from tiles [n, 3] int32 = (start in
+    perm, count <= 16, slot). x [T, in], y [T, out] bf16; slot pools
+    A [S, R, in], B [S, out, R] with alpha / rank folded into B."""
+    if _use_hip(x):
+        _ext.lora_add(y, x, A, B, perm, tiles)
+        return
+    ref.lora_add(y, x, A, B, perm, tiles)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

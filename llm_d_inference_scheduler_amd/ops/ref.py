@@ -7,6 +7,7 @@ input dtype, mirroring the kernels' internal precision.
 """
 from typing import Optional
 
+import numpy as np
 import torch
 
 FP8_E4M3_MAX = 448.0
@@ -653,6 +654,40 @@ class PrefixModel:
                         out[r, e] = b + 1
                 active = self.next_active(active, surv, b, full)
         return torch.from_numpy(out)
+
+
+LORA_TILE = 16     # rows of one work-list tile (one MFMA row block)
+
+
+def lora_worklist(row_slot):
+    """The LoRA work list of a batch (DEVELOPMENT.md "LoRA adapters"):
+    row_slot holds each row's adapter slot, -1 for none. Returns (perm,
+    tiles) as CPU int32 tensors: perm lists the adapter rows grouped by slot
+    (rows of one slot in ascending order), tiles [n, 3] holds (start in perm,
+    count <= 16, slot). Rows with no adapter appear in neither."""
+    rs = np.asarray(row_slot, dtype=np.int64).reshape(-1)
+    rows = np.nonzero(rs >= 0)[0]
+    rows = rows[np.argsort(rs[rows], kind="stable")]
+    slots, starts, counts = np.unique(rs[rows], return_index=True,
+                                      return_counts=True)
+    tiles = [(start + i, min(LORA_TILE, count - i), slot)
+             for slot, start, count in zip(slots.tolist(), starts.tolist(),
+                                           counts.tolist())
+             for i in range(0, count, LORA_TILE)]
+    return (torch.from_numpy(rows.astype(np.int32)),
+            torch.tensor(tiles, dtype=torch.int32).reshape(-1, 3))
+
+
+def lora_add(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+             B: torch.Tensor, perm: torch.Tensor, tiles: torch.Tensor) -> None:
+    """y[row] += (x[row] · A[slot]ᵀ) · B[slot]ᵀ in place for the rows of
+    perm, the slot taken from the row's tile. x [T, in], y [T, out];
+    A [S, R, in], B [S, out, R]. fp32 maths, the intermediate rounded to
+    x's dtype as the kernel does; rows outside perm are not touched."""
+    for start, count, slot in tiles.tolist():
+        rows = perm[start:start + count].long()
+        tmp = (x[rows].float() @ A[slot].float().T).to(x.dtype).float()
+        y[rows] = (y[rows].float() + tmp @ B[slot].float().T).to(y.dtype)
 
 
 _PREFIX_MODEL = PrefixModel()

@@ -302,14 +302,22 @@ class PrecisePrefixCacheScorer(Scorer):
         self.block_size = int(params.get("blockSize", 16))
         self.index = KVBlockIndex(
             float(params.get("speculativeTTLSeconds", 2.0)))
+        # names the engines serve as LoRA adapters (the node sets it): a
+        # request whose target_model is one hashes with the adapter's seed,
+        # as the engine does; any other name is the base model
+        self.adapter_names: set = set()
 
     def _hashes(self, ctx: SchedulingContext):
         cached = getattr(ctx, "_precise_hashes", None)
         if cached is not None:
             return cached
         from ..engine.kvcache import block_hashes
+        from ..engine.lora import adapter_hash_seed
         toks = ctx.request.prompt_tokens or []
-        h = [int(x) for x in block_hashes(toks, self.block_size)]
+        target = ctx.request.target_model
+        seed = adapter_hash_seed(
+            target if target in self.adapter_names else "")
+        h = [int(x) for x in block_hashes(toks, self.block_size, seed)]
         ctx._precise_hashes = h
         return h
 

@@ -41,12 +41,33 @@ def parse_args(argv=None):
                         '"calibrate" (synthetic tokens at start-up) or the '
                         'path of a scales JSON; default: $LLMD_KV_SCALES, '
                         'else "none"')
+    p.add_argument("--max-loras", type=int, default=0,
+                   help="LoRA adapters resident at once (0 = LoRA off)")
+    p.add_argument("--max-lora-rank", type=int, default=16,
+                   help="rank of the adapter slot pools (rounded up to a "
+                        "multiple of 16, at most 64)")
+    p.add_argument("--lora", action="append", default=[],
+                   metavar="NAME=SPEC",
+                   help="serve an adapter under NAME: SPEC is a file saved "
+                        "by LoraAdapter.save or random:rank=R,seed=S; "
+                        "repeatable")
     p.add_argument("--flow-control", action="store_true",
                    help="enable the flowControl feature gate")
     p.add_argument("--decode-chunk-tokens", type=int, default=0)
     p.add_argument("--device", default=None)
     p.add_argument("--seed", type=int, default=0)
     return p.parse_args(argv)
+
+
+def parse_lora_args(items):
+    """--lora NAME=SPEC ... -> {name: spec}."""
+    out = {}
+    for item in items:
+        name, sep, spec = item.partition("=")
+        if not sep or not name or not spec:
+            raise SystemExit(f"--lora wants NAME=SPEC, got {item!r}")
+        out[name] = spec
+    return out
 
 
 def build_node(args):
@@ -81,7 +102,9 @@ def build_node(args):
         kv_cache_dtype=args.kv_dtype,
         flow_control=args.flow_control,
         decode_chunk_tokens=args.decode_chunk_tokens or None,
-        seed=args.seed, **scale_kw)
+        seed=args.seed, max_loras=args.max_loras,
+        max_lora_rank=args.max_lora_rank,
+        lora_adapters=parse_lora_args(args.lora), **scale_kw)
     return NodeRunner(cfg)
 
 

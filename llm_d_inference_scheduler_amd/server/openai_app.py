@@ -220,9 +220,13 @@ def build_app(service: NodeService,
 
     @app.get("/v1/models")
     async def models():
+        base = service.node.cfg.model.name
+        owner = "llm-d-inference-scheduler-amd"
+        # the base model first, then each LoRA adapter it serves
         return {"object": "list", "data": [
-            {"id": service.node.cfg.model.name, "object": "model",
-             "owned_by": "llm-d-inference-scheduler-amd"}]}
+            {"id": base, "object": "model", "owned_by": owner}] + [
+            {"id": name, "object": "model", "owned_by": owner,
+             "parent": base} for name in service.node.engine.adapters]}
 
     @app.post("/tokenize")
     async def tokenize(request: Request):

@@ -39,6 +39,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/flash_prefill.hip",
         "csrc/hip/flash_prefill_glds.hip",
         "csrc/hip/sampler.hip",
+        "csrc/hip/lora.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],
