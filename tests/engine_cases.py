@@ -17,12 +17,15 @@ itself, the token before it, and the first tokens of its sequence.
 tests/test_engine_cases.py proves on the CPU that the faults listed there
 move the worst row by more than 10x the limit the GPU tier asserts.
 """
+import dataclasses
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
+from llm_d_inference_scheduler_amd import ops
+from llm_d_inference_scheduler_amd.datalayer.endpoint import Role
 from llm_d_inference_scheduler_amd.engine import EngineRequest, EngineWorker
 from llm_d_inference_scheduler_amd.models.configs import ModelConfig
 
@@ -33,15 +36,19 @@ CONFIG = ModelConfig(
     intermediate_size=512, num_layers=2, num_heads=4, num_kv_heads=2,
     head_dim=128, rope_theta=10000.0, max_position=1024)
 
+# The same block with Qwen3's per-head QK-RMSNorm (scenario Q)
+CONFIG_QK = dataclasses.replace(CONFIG, qk_norm=True)
+
 SHARPEN_SEED = 1234
 
 
-def make_worker(device, dtype=torch.bfloat16, **kw) -> EngineWorker:
+def make_worker(device, dtype=torch.bfloat16, config=CONFIG,
+                **kw) -> EngineWorker:
     """A sharpened worker whose pass boundaries do not depend on the
     wall clock (prefill_min_tokens=1, prefill_max_delay_ms=0)."""
     kw.setdefault("kv_blocks", 256)
     kw.setdefault("max_model_len", 1024)
-    worker = EngineWorker(CONFIG, device, dtype=dtype, prefill_min_tokens=1,
+    worker = EngineWorker(config, device, dtype=dtype, prefill_min_tokens=1,
                           prefill_max_delay_ms=0.0, overlap_streams=False,
                           **kw)
     sharpen(worker.model, SHARPEN_SEED)
@@ -79,8 +86,13 @@ def dense_logits64(model, tokens: List[int]) -> torch.Tensor:
         h = _rms64(x, f64(layer["input_norm"]), c.rms_eps)
         q, k, v = (h @ f64(layer["wqkv"])).split(
             [c.q_size, c.kv_size, c.kv_size], dim=-1)
-        q = _rope64(q.view(T, c.num_heads, c.head_dim), cos, sin)
-        k = _rope64(k.view(T, c.num_kv_heads, c.head_dim), cos, sin)
+        q = q.view(T, c.num_heads, c.head_dim)
+        k = k.view(T, c.num_kv_heads, c.head_dim)
+        if c.qk_norm:
+            q = _rms64(q, f64(layer["q_norm"]), c.rms_eps)
+            k = _rms64(k, f64(layer["k_norm"]), c.rms_eps)
+        q = _rope64(q, cos, sin)
+        k = _rope64(k, cos, sin)
         v = v.view(T, c.num_kv_heads, c.head_dim)
         k = k.repeat_interleave(qpg, dim=1)           # [T, QH, D]
         v = v.repeat_interleave(qpg, dim=1)
@@ -109,6 +121,15 @@ SINK_TOKENS = tuple(range(496, 512))
 N_SINKS = 4           # sink tokens at the head of every prompt
 WO_GAIN = 8.0
 HEAD_GAIN = (1.0, 1.0, 1.0, 1.0)   # per query head, on top of WO_GAIN
+# cfg.qk_norm: the q_norm / k_norm gains, uniform per element; QK_GAIN on the
+# RoPE pairs no designed head reads, the narrower ranges on the pairs the
+# position heads and the sink head read (see sharpen)
+QK_GAIN = (0.5, 2.0)
+QK_GAIN_HIGH = (1.8, 2.0)
+QK_GAIN_LOW = (0.5, 0.7)
+QK_GAIN_MID = (1.8, 2.0)
+QK_K_BOOST = 3.0      # K's image of c on the fast pairs, times this
+QK_HEAD_GAIN = (1.5, 1.5, 1.5, 2.25)   # HEAD_GAIN under cfg.qk_norm
 
 
 def sharpen(model, seed: int) -> None:
@@ -136,9 +157,39 @@ def sharpen(model, seed: int) -> None:
 
     So the newest token, the tokens just before it and the first block each
     hold O(1) of some head's weight at any sequence length, and what a row
-    attends to changes from one position to the next."""
+    attends to changes from one position to the next.
+
+    With cfg.qk_norm every head's q and k are normalised to an RMS of 1 and
+    multiplied by the layer's q_norm / k_norm gains gq, gk before RoPE, so
+    the scale of a q column no longer sets a peak: the gains do.
+
+    - gq and gk are drawn per layer and per element, all different from
+      each other and from 1: from QK_GAIN on the RoPE pairs no designed
+      head reads; on the fast and the slow pairs gq from QK_GAIN_HIGH in
+      the first half of a pair and QK_GAIN_LOW in the second, gk from
+      QK_GAIN_MID. So gq * gk differs between the halves of a pair (a gain
+      applied behind RoPE does not commute with the rotation) and so does
+      gq / gk (swapped gains change the scores); two gains with opposite
+      halves were tried first and hid a norm behind RoPE, their product
+      being the same in both halves.
+    - A position head's q column is R(-off)(kc * gk) / gq: behind norm and
+      gain it is the matched filter of the gained common image of K, and
+      the peak stays at s = t - off. K's image of c holds 1/8 of a
+      normalised k on the 16 fast pairs, 4 nats at unit gains: K's columns
+      carry it QK_K_BOOST times, which with the gains gives well over the
+      10 nats of the plain design.
+    - The sink head's q stays a constant on the slow pairs; the sink
+      direction is K's image of it under gq * gk. A sink token's k has
+      about 6.5 nats on it at unit gains, about twice that under them.
+    - Head 0 needs nothing: q and k of a token are one normalised vector
+      (up to the boost), and q_t.k_t = sum(n^2 gq gk) is the largest score
+      it reaches.
+    - wo carries QK_HEAD_GAIN per head on top of WO_GAIN. The QK_ knobs
+      were set so that every fault of tests/test_engine_cases.py moves the
+      560-token request by more than 10x the limit; the ratios are in
+      DEVELOPMENT.md."""
     c = model.cfg
-    assert c.num_heads == 4 and c.num_kv_heads == 2 and not c.qk_norm
+    assert c.num_heads == 4 and c.num_kv_heads == 2
     H, D = c.hidden_size, c.head_dim
     half = D // 2
     gen = torch.Generator(device="cpu").manual_seed(seed)
@@ -175,6 +226,18 @@ def sharpen(model, seed: int) -> None:
     slow[SINK_SLOW:half] = 1.0
     slow[half + SINK_SLOW:] = 1.0
     sink_dir = None
+
+    def gains(first, second):
+        """One gain vector [D] of a QK-norm, drawn after the layer's wqkv:
+        on the RoPE pairs the designed heads read from `first` (first
+        halves) and `second` (second halves), from QK_GAIN elsewhere."""
+        def uniform(lo, hi):
+            return torch.empty(D, dtype=torch.float32).uniform_(
+                lo, hi, generator=gen)
+        read = torch.where(torch.arange(D) < half, uniform(*first),
+                           uniform(*second))
+        return torch.where(fast + slow > 0, read, uniform(*QK_GAIN))
+
     for li, layer in enumerate(model.layers):
         wqkv = randn(H, c.q_size + 2 * c.kv_size, std=QKV_STD)
         q = wqkv[:, :c.q_size].view(H, c.num_heads, D)
@@ -182,24 +245,37 @@ def sharpen(model, seed: int) -> None:
         wqkv[:, c.q_size + c.kv_size:] = blind(
             wqkv[:, c.q_size + c.kv_size:])
         k[:, 0] = q[:, 0]
+        gq = gk = None
+        if c.qk_norm:
+            gq = gains(QK_GAIN_HIGH, QK_GAIN_LOW)
+            gk = gains(QK_GAIN_MID, QK_GAIN_MID)
         for head, kvh, off in ((1, 0, POS_OFFSETS[0]), (2, 1, POS_OFFSETS[1])):
             # every k_s holds cx * kc; q = g * cx * R(-off) kc peaks at
             # s = t - off with g * cx^2 * |kc|^2 / sqrt(D)
             kc = (common @ k[:, kvh]) * fast
+            if c.qk_norm:
+                k[:, kvh] += (QK_K_BOOST - 1.0) * torch.outer(common, kc)
+                kc = QK_K_BOOST * kc
+                # q's length is normalised away
+                q[:, head] = torch.outer(common, rotated(kc * gk, -off) / gq)
+                continue
             g = POS_PEAK * math.sqrt(D) / (cx * cx * float(kc.dot(kc)))
             q[:, head] = g * torch.outer(common, rotated(kc, -off))
         # a sink token carries sqrt(H) / 2 of u, which K maps onto r
-        u = k[:, 1] @ slow
-        g = SINK_PEAK * math.sqrt(D) / (
+        u = k[:, 1] @ (slow * gq * gk if c.qk_norm else slow)
+        g = 1.0 if c.qk_norm else SINK_PEAK * math.sqrt(D) / (
             cx * float(u.norm()) * math.sqrt(H) / 2)
         q[:, 3] = g * torch.outer(common, slow)
         if li == 0:
             sink_dir = blind(u.unsqueeze(1)).squeeze(1)
             sink_dir /= sink_dir.norm()
         put(layer["wqkv"], wqkv)
+        if c.qk_norm:
+            put(layer["q_norm"], gq)
+            put(layer["k_norm"], gk)
         wo = randn(c.q_size, H, std=0.02 / math.sqrt(2 * c.num_layers))
         wo = wo.view(c.num_heads, D, H) * WO_GAIN * torch.tensor(
-            HEAD_GAIN).view(-1, 1, 1)
+            QK_HEAD_GAIN if c.qk_norm else HEAD_GAIN).view(-1, 1, 1)
         put(layer["wo"], wo.view(c.q_size, H))
         put(layer["wgate_up"], blind(
             randn(H, 2 * c.intermediate_size, std=0.02)))
@@ -267,6 +343,7 @@ class Recorder:
         self.records: List[Record] = []
         self.current: List[Tuple[str, int, int, int]] = []
         self.outputs = []
+        self.logprobs: Dict[str, List[float]] = {}
         self._before: Dict[str, int] = {}
         self._forward = worker.model.forward
         self._prefill_pass = worker._prefill_pass
@@ -354,7 +431,154 @@ def run_scenario(worker: EngineWorker, arrivals, max_steps: int = 400,
             raise AssertionError("scenario did not finish")
     finally:
         rec.close()
+    rec.logprobs = _logprobs_of(rec.outputs)
     return rec, {rid: prompts[rid] + generated[rid] for rid in prompts}
+
+
+def _logprobs_of(outputs) -> Dict[str, List[float]]:
+    """{request id: the logprob of every emitted token, by completion
+    index} for the requests whose outputs carry them."""
+    lps: Dict[str, List[float]] = {}
+    for out in outputs:
+        if out.new_logprobs:
+            assert len(out.new_logprobs) == len(out.new_tokens), out
+            lps.setdefault(out.request_id, []).extend(out.new_logprobs)
+    return lps
+
+
+# ---- the prefill -> decode hand-off ------------------------------------------
+
+@dataclass
+class Handoff:
+    """An arrival of run_handoff that prefills on P and decodes on D. kw:
+    further EngineRequest fields (the sampler's)."""
+    rid: str
+    prompt: List[int]
+    max_tokens: int
+    kw: dict = field(default_factory=dict)
+
+    def make(self, **extra) -> EngineRequest:
+        return EngineRequest(self.rid, prompt_tokens=list(self.prompt),
+                             max_tokens=self.max_tokens, **self.kw, **extra)
+
+
+class HandoffFault:
+    """What run_handoff passes between the two workers goes through these
+    hooks; tests/test_engine_cases.py overrides them one at a time."""
+
+    def copied(self, rid, src, dst):
+        """The (source, destination) block ids the copy really moves."""
+        return src, dst
+
+    def seq_len(self, rid, n):
+        return n
+
+    def first_token(self, rid, tok):
+        return tok
+
+    def adopted(self, worker, rid, dst) -> None:
+        """Runs after admit_transferred on the decode worker."""
+
+
+COPIES = ("peer", "staged", "index")
+
+
+def copy_blocks(copy: str, P: EngineWorker, D: EngineWorker,
+                src: List[int], dst: List[int]) -> None:
+    """Blocks src of P's pool into blocks dst of D's: "peer" through
+    copy_blocks_peer (GPU only), "staged" through a move_blocks gather and a
+    move_blocks scatter, "index" by tensor indexing (CPU only)."""
+    sp, dp = P.pool.tensor, D.pool.tensor
+    ids = lambda b: torch.tensor(b, dtype=torch.int32, device=sp.device)
+    if copy == "peer":
+        ops.hip_ops().copy_blocks_peer(sp.data_ptr(), dp, ids(src), ids(dst),
+                                       P.pool.num_blocks)
+        torch.cuda.synchronize()
+    elif copy == "staged":
+        staging = torch.empty(
+            (len(src), sp.shape[0], 2) + tuple(sp.shape[3:]), dtype=sp.dtype,
+            device=sp.device)
+        ops.move_blocks(sp, staging, ids(src), False)
+        ops.move_blocks(dp, staging, ids(dst), True)
+    else:
+        assert copy == "index" and sp.device.type == "cpu", copy
+        dp[:, :, ids(dst).long()] = sp[:, :, ids(src).long()]
+
+
+def run_handoff(P: EngineWorker, D: EngineWorker, actions, copy: str,
+                max_steps: int = 400, mutate: Optional[Callable] = None,
+                fault: Optional[HandoffFault] = None):
+    """run_scenario over a prefill worker P and a decode worker D. actions
+    is a list of (step of D, EngineRequest | Handoff): a request is added to
+    D; a Handoff is prefilled on P (prefill_only) up to its prefill_done,
+    its blocks are copied into blocks taken from D, and D adopts it, all
+    before that step of D runs. Returns P's and D's recorders, {request id:
+    prompt + generated} (for a Handoff: prompt + first_token + what D
+    emitted), D's requests and {request id: (source, destination) ids}.
+    mutate goes to D's recorder."""
+    fault = fault or HandoffFault()
+    rec_p, rec_d = Recorder(P), Recorder(D, mutate)
+    prompts = {a.rid if isinstance(a, Handoff) else a.request_id:
+               list(a.prompt if isinstance(a, Handoff) else a.prompt_tokens)
+               for _, a in actions}
+    generated = {rid: [] for rid in prompts}
+    reqs: Dict[str, EngineRequest] = {}
+    moves: Dict[str, Tuple[List[int], List[int]]] = {}
+
+    def hand_off(h: Handoff) -> None:
+        P.add_request(h.make(prefill_only=True))
+        pd = None
+        for _ in range(max_steps):
+            for out in P.step():
+                assert not out.error, out
+                rec_p.outputs.append(out)
+                if out.kind == "prefill_done":
+                    assert out.request_id == h.rid
+                    pd = out
+            if pd is not None:
+                break
+        else:
+            raise AssertionError("no prefill_done for " + h.rid)
+        src = list(pd.kv_blocks)
+        dst = D.mgr.take_blocks(len(src))
+        assert dst is not None, "the decode worker is out of blocks"
+        copy_blocks(copy, P, D, *fault.copied(h.rid, list(src), list(dst)))
+        req = reqs[h.rid] = h.make()
+        D.admit_transferred(
+            req, dst, fault.seq_len(h.rid, pd.seq_len),
+            fault.first_token(h.rid, pd.first_token),
+            first_logprob=pd.new_logprobs[0] if pd.new_logprobs else None)
+        P.release_prefilled(h.rid)
+        fault.adopted(D, h.rid, dst)
+        moves[h.rid] = (src, dst)
+        # first_token, with its logprob, is the request's first output
+        rec_d.outputs.append(pd)
+        generated[h.rid].extend(pd.new_tokens)
+
+    pending = sorted(actions, key=lambda a: a[0])
+    try:
+        for step in range(max_steps):
+            while pending and pending[0][0] <= step:
+                act = pending.pop(0)[1]
+                if isinstance(act, Handoff):
+                    hand_off(act)
+                else:
+                    reqs[act.request_id] = act
+                    D.add_request(act)
+            for out in D.step():
+                rec_d.outputs.append(out)
+                assert not out.error, out
+                generated[out.request_id].extend(out.new_tokens)
+            if not pending and not D.has_work:
+                break
+        else:
+            raise AssertionError("scenario did not finish")
+    finally:
+        rec_p.close()
+        rec_d.close()
+    rec_d.logprobs = _logprobs_of(rec_d.outputs)
+    hist = {rid: prompts[rid] + generated[rid] for rid in prompts}
+    return rec_p, rec_d, hist, reqs, moves
 
 
 # ---- judging --------------------------------------------------------------
@@ -378,17 +602,66 @@ def judge(records: List[Record], histories: Dict[str, List[int]], model,
     return worst
 
 
+def replay_draw(req: EngineRequest, row: torch.Tensor, n: int,
+                history: List[int], dtype) -> Tuple[int, float]:
+    """(token, logprob) of completion index n of a request with sampler
+    fields, from the recorded logits row of the position before it: what
+    ops.ref.sample returns on the row (cast back to the engine's logits
+    dtype, which is exact) for the request's own temperature, top_k, top_p,
+    resolved seed and pos = n. A request with penalties, min_p or top-N
+    goes through ops.ref.sample_ext, its token state rebuilt by
+    ops.ref.token_state_fill from the original prompt and the n tokens
+    emitted before."""
+    ref = ops.ref
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    one = lambda v, dt: torch.tensor([v], dtype=dt)
+    seed = req._seed64 & 0xFFFFFFFFFFFFFFFF
+    base = (row.to(dtype).unsqueeze(0), one(req.temperature, f32),
+            one(req.top_k, i32), one(req.top_p, f32),
+            one(seed - (1 << 64) if seed >> 63 else seed, i64), one(n, i32))
+    if not req.uses_ext:
+        tok, lp, _, _ = ref.sample(*base)
+        return int(tok), float(lp)
+    state, state_row = None, -1
+    if req.needs_token_state:
+        V = row.shape[0]
+        seen = history[:req.orig_prompt_len + n]
+        state, state_row = ref.token_state_alloc(1, V, "cpu"), 0
+        ref.token_state_fill(
+            state, one(0, i32), torch.tensor(seen, dtype=i32),
+            torch.tensor([0, len(seen)], dtype=i64),
+            one(req.orig_prompt_len, i32), V)
+    tok, lp = ref.sample_ext(
+        *base, one(req.repetition_penalty, f32),
+        one(req.presence_penalty, f32), one(req.frequency_penalty, f32),
+        one(req.min_p, f32), one(0, i32), one(state_row, i32), state, 0)[:2]
+    return int(tok), float(lp)
+
+
+LOGPROB_TOL = 1e-5
+
+
 def check_token_path(records: List[Record], histories: Dict[str, List[int]],
-                     prompt_lens: Dict[str, int]) -> None:
-    """Exact checks on the path of the tokens (greedy requests only):
+                     prompt_lens: Dict[str, int],
+                     reqs: Optional[Dict[str, EngineRequest]] = None,
+                     logprobs: Optional[Dict[str, List[float]]] = None,
+                     dtype=torch.bfloat16) -> None:
+    """Exact checks on the path of the tokens:
 
     - every input row the engine fed the model holds the history's token
       of its position: prompt chunks, and for a decode row the token the
       engine emitted one step before;
     - every emitted token has a recorded logits row, that of the position
-      before it, and its logit equals the row's maximum;
+      before it. For a greedy request its logit equals the row's maximum.
+      For a request of `reqs` with sampler fields it is the token
+      replay_draw gives for its completion index on that row, whichever
+      worker, decode row or pass drew it, and a recorded logprob
+      (`logprobs`: per request, by completion index) is the replay's to
+      within LOGPROB_TOL; dtype is the engine's logits dtype;
     - no position is fed twice without a preemption in between, and every
       position below the last is fed."""
+    reqs = reqs or {}
+    logprobs = logprobs or {}
     row_of = {}
     for rec in records:
         for rid, start, end, row0 in rec.spans:
@@ -398,12 +671,29 @@ def check_token_path(records: List[Record], histories: Dict[str, List[int]],
         for i, key in enumerate(rec.rows):
             row_of.setdefault(key, []).append(rec.logits[i])
     for rid, hist in histories.items():
+        req = reqs.get(rid)
+        sampled = req is not None and req.uses_sampler
+        if sampled:
+            assert req.orig_prompt_len == prompt_lens[rid]
+        lps = logprobs.get(rid)
+        if sampled and req.logprobs:
+            assert lps is not None and \
+                len(lps) == len(hist) - prompt_lens[rid], ("logprobs", rid)
         for pos in range(prompt_lens[rid], len(hist)):
             rows = row_of.get((rid, pos - 1))
             assert rows, ("no logits row", rid, pos - 1)
+            n = pos - prompt_lens[rid]
             for row in rows:
-                assert float(row[hist[pos]]) == float(row.max()), \
-                    ("emitted token is not the argmax", rid, pos)
+                if not sampled:
+                    assert float(row[hist[pos]]) == float(row.max()), \
+                        ("emitted token is not the argmax", rid, pos)
+                    continue
+                tok, lp = replay_draw(req, row, n, hist, dtype)
+                assert tok == hist[pos], \
+                    ("replay", rid, n, "token", hist[pos], tok)
+                if req.logprobs:
+                    assert abs(lps[n] - lp) <= LOGPROB_TOL, \
+                        ("replay", rid, n, "logprob", lps[n], lp)
 
 
 def long_prompt(n: int, salt: int = 0, alphabet: int = 23) -> List[int]:
@@ -464,12 +754,112 @@ def scenario_c():
     return dict(worker=dict(kv_blocks=20), arrivals=arrivals)
 
 
-SCENARIOS = {"A": scenario_a, "B": scenario_b, "C": scenario_c}
+def scenario_h():
+    """The prefill -> decode hand-off into a busy decode worker (run_handoff;
+    `worker` is D, `prefill` is P, which prefills in 48-token chunks).
+
+    - d0, local on D: a live decode row and blocks in use when each
+      hand-off arrives.
+    - h1, handed off at D's step 3: 530 = 33 * 16 + 2 tokens, so the last
+      block is partial and D's first decode store lands in row 3 of a
+      transferred block (first_token took row 2); from then on every decode
+      of D has max_seq_len > 512: the split kernel over one long adopted
+      row and short ones.
+    - h2, handed off at step 5: the shared prefix + 32 = 96 tokens, a
+      multiple of the block size, so D's first decode token needs a block
+      D allocates itself.
+    - h4, handed off at step 7: 40 tokens, seeded top-k sampling with
+      logprobs. P draws its first token at pos 0, D the rest from pos 1.
+    - h3, local on D at step 9: the shared prefix + 41 other tokens. Its
+      prefix can only come from the blocks admit_transferred registered
+      for h2."""
+    h2 = SHARED_PREFIX + [(5 * i + 11) % 23 + 40 for i in range(32)]
+    h3 = SHARED_PREFIX + [(3 * i * i + 2) % 23 + 70 for i in range(41)]
+    h4 = dict(temperature=0.8, top_k=8, seed=4004, logprobs=True)
+    return dict(
+        worker=dict(kv_blocks=256, prefill_chunk_tokens=256,
+                    role=Role.DECODE),
+        prefill=dict(kv_blocks=256, prefill_chunk_tokens=48,
+                     role=Role.PREFILL),
+        actions=[(0, _req("d0", long_prompt(150, salt=3), 30)),
+                 (3, Handoff("h1", long_prompt(530, salt=4), 10)),
+                 (5, Handoff("h2", h2, 8)),
+                 (7, Handoff("h4", long_prompt(40, salt=5), 6, h4)),
+                 (9, _req("h3", h3, 4))])
+
+
+# What the KV pools of a hand-off scenario hold before anything is stored:
+# finite, so a masked row contributes exp(-inf) * POISON = 0 as a zero
+# would, and large, so a row that is read swamps the output (a score of
+# POISON * sum(q) / sqrt(D), tens of nats either way, and V = POISON).
+POISON = 32.0
+
+
+def shuffle_free_list(mgr) -> None:
+    """Take every free block and release them in a scattered order (the
+    free list is served oldest first): what the manager hands out
+    afterwards is neither ascending nor what a fresh manager hands out."""
+    blocks = mgr.take_blocks(mgr.free_blocks)
+    n = len(blocks)
+    assert math.gcd(37, n) == 1
+    mgr.release_blocks([blocks[(37 * i + 11) % n] for i in range(n)])
+    assert mgr.free_blocks == n
+
+
+# kind -> sampler fields of scenario S; `seed` is added per request
+S_KINDS = {
+    "greedy": dict(),
+    "topk": dict(temperature=0.8, top_k=8),
+    "topp": dict(temperature=1.0, top_p=0.9, logprobs=True),
+    "pen": dict(repetition_penalty=1.3, frequency_penalty=0.5),
+    "minp": dict(min_p=0.1, top_logprobs=3),
+}
+# By request index of scenario B. With S_MAX_TOKENS and S_KV_BLOCKS r1, r2
+# and r3 are preempted: a top-p, the penalised and a top-k request. Rows
+# pass from r0 to r5 and from r6 to r9 (seeded to greedy) and from r2 to r3
+# and to r8 (to another seed).
+S_MIX = ["topk", "topp", "pen", "topk", "greedy", "greedy", "topp", "minp",
+         "topk", "greedy"]
+# B's outputs are too short to run a pool dry while they decode
+S_MAX_TOKENS = [30, 12, 20, 28, 22, 26, 18, 20, 24, 22]
+S_KV_BLOCKS = 32
+
+
+def scenario_s():
+    """Sampled decoding: scenario B's ten requests over a decode state of 4
+    rows, with S_MIX's sampler fields (every non-greedy request has a seed
+    of its own, so every step it takes part in goes through the fused
+    sampler), in a pool small enough that requests are preempted and
+    recomputed."""
+    sc = scenario_b()
+    arrivals = []
+    for i, (at, base) in enumerate(sc["arrivals"]):
+        kw = dict(S_KINDS[S_MIX[i]])
+        if kw:
+            kw["seed"] = 7000 + 13 * i
+        arrivals.append((at, EngineRequest(
+            base.request_id, prompt_tokens=list(base.prompt_tokens),
+            max_tokens=S_MAX_TOKENS[i], **kw)))
+    return dict(worker=dict(sc["worker"], kv_blocks=S_KV_BLOCKS),
+                arrivals=arrivals)
+
+
+def scenario_q():
+    """Scenario A under QK-norm: the unfused chain with its two rmsnorm
+    launches on [T * H, D] views, q_norm and k_norm gains that differ from
+    each other and from 1 (sharpen)."""
+    return dict(scenario_a(), config=CONFIG_QK)
+
+
+SCENARIOS = {"A": scenario_a, "B": scenario_b, "C": scenario_c,
+             "H": scenario_h, "S": scenario_s, "Q": scenario_q}
 
 # The worst row error of the bf16 CPU worker (ops.ref) per scenario, as
 # measured (7.43e-3, 7.96e-3, 7.86e-3) and rounded up to two digits; the
 # device limit is LIMIT_FACTOR times it.
 CPU_WORST = {"A": 0.0075, "B": 0.0080, "C": 0.0079}
+# H, S and Q likewise (8.645e-3, 7.996e-3, 7.699e-3)
+CPU_WORST.update({"H": 0.0087, "S": 0.0080, "Q": 0.0077})
 LIMIT_FACTOR = 4.0
 
 
@@ -485,23 +875,65 @@ class Result:
     worst: Dict[str, float]
     plens: Dict[str, int]
     reqs: Dict[str, EngineRequest]
+    # the judged records: the worker's, or for a hand-off scenario P's (the
+    # chunks and the last prompt row) followed by D's
+    records: Optional[List[Record]] = None
+    # hand-off scenarios: worker and rec are D's
+    prefill_worker: Optional[EngineWorker] = None
+    prefill_rec: Optional[Recorder] = None
+    moves: Optional[Dict[str, Tuple[List[int], List[int]]]] = None
+
+    def __post_init__(self):
+        if self.records is None:
+            self.records = self.rec.records
 
     def __iter__(self):
         return iter((self.worker, self.rec, self.hist, self.worst,
                      self.plens))
 
+    def check_token_path(self) -> None:
+        check_token_path(self.records, self.hist, self.plens, self.reqs,
+                         self.rec.logprobs, self.worker.dtype)
+
 
 def run(name: str, device, dtype=torch.bfloat16, mutate=None,
-        setup=None) -> Result:
-    """Run a scenario on a fresh worker and judge it."""
+        setup=None, copy: Optional[str] = None,
+        fault: Optional[HandoffFault] = None, ref_model=None) -> Result:
+    """Run a scenario on a fresh worker and judge it. copy, fault: of a
+    hand-off scenario (copy defaults to "index" on the CPU and "staged"
+    elsewhere). ref_model: the model whose weights the reference reads,
+    where setup has changed the worker's."""
     sc = SCENARIOS[name]()
-    worker = make_worker(device, dtype, **sc["worker"])
+    config = sc.get("config", CONFIG)
+    worker = make_worker(device, dtype, config, **sc["worker"])
+    if "actions" in sc:
+        assert setup is None and ref_model is None
+        if copy is None:
+            copy = "index" if worker.device.type == "cpu" else "staged"
+        P = make_worker(device, dtype, config, **sc["prefill"])
+        shuffle_free_list(worker.mgr)
+        # Both pools start poisoned, as the kernel edge tests poison
+        # theirs: a row that no token was stored in holds POISON in K and
+        # V. Such rows lie behind a sequence's length and must never be
+        # read; a block that lands in another table entry than its own
+        # brings the unwritten rows of a partial block inside it.
+        P.pool.tensor.fill_(POISON)
+        worker.pool.tensor.fill_(POISON)
+        plens = {a.rid if isinstance(a, Handoff) else a.request_id:
+                 len(a.prompt if isinstance(a, Handoff) else a.prompt_tokens)
+                 for _, a in sc["actions"]}
+        rec_p, rec, hist, reqs, moves = run_handoff(
+            P, worker, sc["actions"], copy, mutate=mutate, fault=fault)
+        records = rec_p.records + rec.records
+        worst = judge(records, hist, worker.model)
+        return Result(worker, rec, hist, worst, plens, reqs, records, P,
+                      rec_p, moves)
     if setup is not None:
         setup(worker)
     reqs = {r.request_id: r for _, r in sc["arrivals"]}
     plens = {rid: len(r.prompt_tokens) for rid, r in reqs.items()}
     rec, hist = run_scenario(worker, sc["arrivals"], mutate=mutate)
-    worst = judge(rec.records, hist, worker.model)
+    worst = judge(rec.records, hist, ref_model or worker.model)
     return Result(worker, rec, hist, worst, plens, reqs)
 
 
@@ -556,6 +988,111 @@ def check_scenario_b(res: Result) -> None:
                for x, y in zip(occ, occ[1:])), occupants
     # rows that were live when the state grew went on decoding afterwards
     assert any(row >= 4 for row in occupants), occupants
+    seeds = {rid: r.seed for rid, r in res.reqs.items()}
+    if any(s is not None for s in seeds.values()):
+        # sampled requests: a row went from a seeded request to a greedy
+        # one, which must not draw, and one to a request with another
+        # seed, which must not inherit the first
+        passed = [(x, y) for occ in occupants.values()
+                  for x, y in zip(occ, occ[1:]) if seeds[x] is not None]
+        assert any(not res.reqs[y].uses_sampler for _, y in passed), \
+            occupants
+        assert any(seeds[y] not in (None, seeds[x]) and
+                   res.reqs[y].temperature > 0 for x, y in passed), occupants
+
+
+def _check_recomputed(res: Result, rid: str) -> None:
+    """The recompute of a preempted request: a prefill over prompt and
+    output after the one that ended the prompt (a request may be preempted
+    before its first decode row), and decode rows after it unless its last
+    row gave the request's last token."""
+    kinds = [(r.is_decode, start, end) for r in res.rec.records
+             for srid, start, end, _ in r.spans if srid == rid]
+    ended = kinds.index(next(k for k in kinds
+                             if not k[0] and k[2] == res.plens[rid]))
+    redo = [i for i, k in enumerate(kinds)
+            if i > ended and not k[0] and k[2] > res.plens[rid]]
+    assert redo, kinds
+    if kinds[redo[-1]][2] + 1 < len(res.hist[rid]):
+        assert any(k[0] for k in kinds[redo[-1]:]), kinds
+
+
+def check_scenario_s(res: Result) -> None:
+    check_scenario_b(res)
+    reqs = res.reqs
+    kinds = sorted((r.temperature, r.top_k, r.top_p, r.repetition_penalty,
+                    r.frequency_penalty, r.min_p, r.top_logprobs, r.logprobs,
+                    r.seed is not None) for r in reqs.values())
+    assert kinds == sorted(
+        [(0.0, 0, 1.0, 1.0, 0.0, 0.0, 0, False, False)] * 3 +
+        [(0.8, 8, 1.0, 1.0, 0.0, 0.0, 0, False, True)] * 3 +
+        [(1.0, 0, 0.9, 1.0, 0.0, 0.0, 0, True, True)] * 2 +
+        [(0.0, 0, 1.0, 1.3, 0.5, 0.0, 0, False, True)] +
+        [(0.0, 0, 1.0, 1.0, 0.0, 0.1, 3, False, True)]), kinds
+    assert len({r.seed for r in reqs.values() if r.seed is not None}) == 7
+    victims = [rid for rid, r in reqs.items()
+               if r.prompt_len > r.orig_prompt_len]
+    # a request that draws (its pos must go on where it stopped) and the
+    # penalised one (its token state must be rebuilt) were preempted
+    assert any(reqs[v].temperature > 0 and reqs[v].seed is not None
+               for v in victims), victims
+    assert any(reqs[v].needs_token_state for v in victims), victims
+    for rid in victims:
+        _check_recomputed(res, rid)
+    fin = {o.request_id: o for o in res.rec.outputs if o.finished}
+    assert set(fin) == set(reqs)
+    assert all(len(res.hist[rid]) - res.plens[rid] == reqs[rid].max_tokens
+               for rid in fin)
+
+
+def check_scenario_h(res: Result) -> None:
+    from llm_d_inference_scheduler_amd.ops.dispatch import split_geometry
+    P, D = res.prefill_worker, res.worker
+    # the destination ids are not the source ids, and not in order
+    assert set(res.moves) == {"h1", "h2", "h4"}
+    for rid, (src, dst) in res.moves.items():
+        assert len(src) == len(dst) == -(-res.plens[rid] // 16), rid
+        assert src != dst, (rid, src, dst)
+    assert any(dst != sorted(dst) for _, dst in res.moves.values())
+    dec = [r for r in res.rec.records if r.is_decode]
+    # P only prefills, in chunks with a prior; D never prefills a
+    # handed-off request
+    assert not any(r.is_decode for r in res.prefill_rec.records)
+    assert any(rid == "h1" and start > 0 and end - start == 48
+               for r in res.prefill_rec.records
+               for rid, start, end, _ in r.spans)
+    assert not any(rid in res.moves for r in res.rec.records
+                   if not r.is_decode for rid, _, _, _ in r.spans)
+    # h1 decodes from the partial block it brought along, by the split
+    # kernel
+    h1 = [r for r in dec if "h1" in {rid for rid, _ in r.rows}]
+    assert [pos for r in h1 for rid, pos in r.rows if rid == "h1"] == \
+        list(range(530, 539))
+    for r in h1:
+        assert r.max_seq_len > 512
+        assert split_geometry(len(r.rows) * CONFIG.num_kv_heads,
+                              r.max_seq_len) is not None
+    # d0 was decoding when each hand-off arrived
+    first = {rid: min(i for i, r in enumerate(dec)
+                      if rid in {x for x, _ in r.rows})
+             for rid in ("d0", "h1", "h2", "h4")}
+    assert first["d0"] < first["h1"] < first["h2"] < first["h4"], first
+    assert any({"d0", "h1", "h2"} <= {rid for rid, _ in r.rows}
+               for r in dec), "no decode batch of d0, h1 and h2"
+    # h2's first decode token went into a block D allocated itself
+    h2_pos = [pos for r in dec for rid, pos in r.rows if rid == "h2"]
+    assert h2_pos[0] == 96 and len(res.moves["h2"][1]) == 6
+    # h3's prefix came from the blocks admit_transferred registered
+    fin = {o.request_id: o for o in res.rec.outputs if o.finished}
+    assert set(fin) == set(res.plens)
+    assert fin["h3"].cached_tokens == 64
+    h3 = [start for r in res.rec.records if not r.is_decode
+          for rid, start, _, _ in r.spans if rid == "h3"]
+    assert h3 and min(h3) == 64, h3
+    # h4 was drawn on both workers
+    assert res.reqs["h4"].uses_sampler and len(res.rec.logprobs["h4"]) == 6
+    assert P.mgr.free_blocks == P.pool.num_blocks
+    assert D.mgr.free_blocks == D.pool.num_blocks
 
 
 def check_scenario_c(res: Result) -> None:

@@ -7,7 +7,11 @@ precision, which checks the reference itself. In bf16 (the ops.ref path) the
 worst row error must stay within the committed CPU_WORST, from which the GPU
 tier takes its limit. Then eight faults of the layer under test, each applied
 to the batch on its way into the model, must each move the worst row of the
-560-token request of scenario A beyond 10x that limit."""
+560-token request of scenario A beyond 10x that limit, and again on scenario
+Q with three faults of the QK-norm chain. Faults of the hand-off (scenario H)
+must do the same to the requests they concern, or fail the exact token-path
+check; faults of the sampler's per-row state (scenario S) must fail the
+replay of the sampled tokens from the recorded rows."""
 import functools
 
 import pytest
@@ -25,18 +29,20 @@ def clean(name, dtype):
 
 @pytest.mark.parametrize("name", sorted(ec.SCENARIOS))
 def test_fp32_engine_matches_dense_reference(name):
-    _, rec, hist, worst, plens = clean(name, torch.float32)
+    res = clean(name, torch.float32)
+    worst = res.worst
     print(f"ENGINE-CPU|{name}|fp32|{max(worst.values()):.3e}")
     assert max(worst.values()) < 1e-4, worst
-    ec.check_token_path(rec.records, hist, plens)
+    res.check_token_path()
 
 
 @pytest.mark.parametrize("name", sorted(ec.SCENARIOS))
 def test_bf16_engine_within_cpu_worst(name):
-    _, rec, hist, worst, plens = clean(name, torch.bfloat16)
+    res = clean(name, torch.bfloat16)
+    worst = res.worst
     print(f"ENGINE-CPU|{name}|bf16|{max(worst.values()):.3e}")
     assert max(worst.values()) <= ec.CPU_WORST[name], worst
-    ec.check_token_path(rec.records, hist, plens)
+    res.check_token_path()
 
 
 def test_scenarios_reach_what_they_are_for():
@@ -44,6 +50,22 @@ def test_scenarios_reach_what_they_are_for():
     ec.check_scenario_a(clean("A", torch.bfloat16))
     ec.check_scenario_b(clean("B", torch.bfloat16))
     ec.check_scenario_c(clean("C", torch.bfloat16))
+    ec.check_scenario_h(clean("H", torch.bfloat16))
+    ec.check_scenario_s(clean("S", torch.bfloat16))
+    q = clean("Q", torch.bfloat16)
+    assert q.worker.cfg.qk_norm
+    ec.check_scenario_a(q)
+
+
+def test_staged_copy_equals_index_copy():
+    """H through the move_blocks gather and scatter gives the logits of the
+    tensor-index copy bit for bit."""
+    a = clean("H", torch.bfloat16)
+    b = ec.run("H", "cpu", torch.bfloat16, copy="staged")
+    assert a.hist == b.hist and a.moves == b.moves
+    assert len(a.records) == len(b.records)
+    for ra, rb in zip(a.records, b.records):
+        assert ra.rows == rb.rows and torch.equal(ra.logits, rb.logits)
 
 
 def test_reference_is_causal_and_unpaged():
@@ -164,6 +186,241 @@ def test_mutant_is_noticed_on_the_long_request(mutant):
     bound = 10 * ec.limit("A")
     print(f"MUTANT|{mutant.__name__}|b|{bound:.3e}|{worst['b']:.3e}|"
           f"{worst['b'] / ec.limit('A'):.1f}x")
+    assert worst["b"] > bound, (mutant.__name__, worst)
+
+
+# ---- H: faults of the hand-off ---------------------------------------------
+
+class BlocksSwappedInCopy(ec.HandoffFault):
+    """Two destination blocks swapped in the copy but not in the table: by
+    default the first and the last.
+
+    Attention over one sequence does not depend on the order of its keys,
+    so a swap between two full blocks of h1 leaves every logit as it was
+    (blocks 0 and 1: worst row of h1 7.926e-3 with and without). A swap
+    with the partial last block shows: 14 rows of the other block end up
+    behind the sequence length, and the 14 rows of the last block that no
+    token was stored in end up inside it. Over zeroed pools those rows
+    read as 14 more keys with a score of 0 and moved h1 to 6.5x the limit
+    of H only; the pools of H start poisoned (ec.POISON), and reading them
+    moves h1 to 45x."""
+    def __init__(self, i=0, j=-1):
+        self.i, self.j = i, j
+
+    def copied(self, rid, src, dst):
+        if len(dst) > max(self.i, self.j, 1):
+            dst[self.i], dst[self.j] = dst[self.j], dst[self.i]
+        return src, dst
+
+
+class LastBlockNotCopied(ec.HandoffFault):
+    def copied(self, rid, src, dst):
+        return src[:-1], dst[:-1]
+
+
+class SeqLenMinusOne(ec.HandoffFault):
+    def seq_len(self, rid, n):
+        return n - 1
+
+
+class SeqLenPlusOne(ec.HandoffFault):
+    def seq_len(self, rid, n):
+        return n + 1
+
+
+class FirstBlockOfH2Zeroed(ec.HandoffFault):
+    def adopted(self, worker, rid, dst):
+        if rid == "h2":
+            worker.pool.tensor[:, :, dst[0]] = 0
+
+
+class WrongFirstToken(ec.HandoffFault):
+    def first_token(self, rid, tok):
+        return (tok + 1) % ec.CONFIG.vocab_size
+
+
+H_MUTANTS = [(BlocksSwappedInCopy, ("h1",)), (LastBlockNotCopied, ("h1",)),
+             (SeqLenMinusOne, ("h1", "h2")), (SeqLenPlusOne, ("h2",)),
+             (FirstBlockOfH2Zeroed, ("h3",))]
+
+
+@pytest.mark.parametrize("fault,judged", H_MUTANTS,
+                         ids=[m[0].__name__ for m in H_MUTANTS])
+def test_handoff_mutant_is_noticed(fault, judged):
+    """Each fault of the hand-off moves the worst row of the named requests
+    beyond 10x the limit the GPU tier asserts for H."""
+    worst = ec.run("H", "cpu", torch.bfloat16, fault=fault()).worst
+    bound = 10 * ec.limit("H")
+    for rid in judged:
+        print(f"MUTANT|H|{fault.__name__}|{rid}|{bound:.3e}|"
+              f"{worst[rid]:.3e}|{worst[rid] / ec.limit('H'):.1f}x")
+    for rid in judged:
+        assert worst[rid] > bound, (fault.__name__, rid, worst)
+
+
+def test_wrong_first_token_fails_the_token_path():
+    """D decodes from another token than the one P emitted: its first
+    decode input is not the history's token of that position."""
+    res = ec.run("H", "cpu", torch.bfloat16, fault=WrongFirstToken())
+    with pytest.raises(AssertionError) as err:
+        res.check_token_path()
+    assert err.value.args[0][0] == "input_ids", err.value
+
+
+# ---- S: faults of the sampler's per-row state --------------------------------
+
+def recomputed(req):
+    return req.prompt_len > req.orig_prompt_len
+
+
+def pos_restarts_after_recompute(worker):
+    """A recomputed request's decode pos starts at 0 again."""
+    st, join = worker.dstate, worker.dstate.join
+
+    def wrapped(req, table, seq_len, *args, **kw):
+        join(req, table, seq_len, *args, **kw)
+        if recomputed(req):
+            st.pos_off[st.row_of[req.request_id]] = -seq_len
+    st.join = wrapped
+
+
+def reused_row_keeps_seed(worker):
+    """join leaves the seed of the row's previous occupant in place."""
+    st, join = worker.dstate, worker.dstate.join
+    used = set()
+
+    def wrapped(req, *args, **kw):
+        row = st.free_rows[-1] if st.free_rows else None
+        old = None if row is None else st.seed[row].clone()
+        join(req, *args, **kw)
+        if row is not None and row in used:
+            assert st.row_of[req.request_id] == row
+            st.seed[row] = old
+        used.add(st.row_of[req.request_id])
+    st.join = wrapped
+
+
+def token_state_not_refilled(worker):
+    """The token state of a recomputed request is not rebuilt."""
+    fill = worker.tstate.fill
+    worker.tstate.fill = lambda reqs: fill(
+        [r for r in reqs if not recomputed(r)])
+
+
+class TopKOfTwoRowsSwapped(Mutant):
+    """Every decode step samples with the top_k of two of its rows
+    swapped (the values live in the decode state, not in the batch)."""
+    def __init__(self):
+        self.undo = None
+
+    def decode(self, batch):
+        st = self.recorder.worker.dstate
+        if self.undo is not None:
+            a, b = self.undo
+            st.top_k[[a, b]] = st.top_k[[b, a]]
+            self.undo = None
+        rows = [st.row_of[rid] for rid, _, _, _ in self.recorder.current]
+        ks = st.top_k[rows].tolist()
+        for i in range(1, len(rows)):
+            if ks[i] != ks[0]:
+                a, b = rows[0], rows[i]
+                st.top_k[[a, b]] = st.top_k[[b, a]]
+                self.undo = (a, b)
+                break
+
+
+S_MUTANTS = [
+    ("pos_restarts_after_recompute",
+     dict(setup=pos_restarts_after_recompute), None),
+    ("reused_row_keeps_seed", dict(setup=reused_row_keeps_seed), None),
+    ("top_k_of_two_rows_swapped", dict(mutate=TopKOfTwoRowsSwapped), None),
+    ("token_state_not_refilled", dict(setup=token_state_not_refilled), "pen"),
+]
+
+
+@pytest.mark.parametrize("name,how,kind", S_MUTANTS,
+                         ids=[m[0] for m in S_MUTANTS])
+def test_sampler_mutant_fails_the_replay(name, how, kind):
+    """Each fault changes a token the replay from the recorded rows does
+    not give; the clean run passes (test_bf16_engine_within_cpu_worst)."""
+    how = {k: v() if k == "mutate" else v for k, v in how.items()}
+    res = ec.run("S", "cpu", torch.bfloat16, **how)
+    with pytest.raises(AssertionError) as err:
+        res.check_token_path()
+    why = err.value.args[0]
+    print(f"MUTANT|S|{name}|{why}")
+    if why[0] == "emitted token is not the argmax":
+        # a greedy row that was made to draw
+        assert kind is None and name == "top_k_of_two_rows_swapped"
+        return
+    assert why[0] == "replay" and why[3] == "token", why
+    if kind == "pen":
+        assert res.reqs[why[1]].needs_token_state, why
+
+
+# ---- Q: faults of the QK-norm ------------------------------------------------
+
+def gains_swapped(worker, ops, mp):
+    for layer in worker.model.layers:
+        layer["q_norm"], layer["k_norm"] = layer["k_norm"], layer["q_norm"]
+
+
+def k_norm_skipped(worker, ops, mp):
+    k_norms = {id(layer["k_norm"]) for layer in worker.model.layers}
+    real = ops.rmsnorm
+
+    def rmsnorm(x, w, eps, **kw):
+        return x if id(w) in k_norms else real(x, w, eps, **kw)
+    mp.setattr(ops, "rmsnorm", rmsnorm)
+
+
+def norm_after_rope(worker, ops, mp):
+    gains = {id(layer[key]) for layer in worker.model.layers
+             for key in ("q_norm", "k_norm")}
+    real_norm, real_rope = ops.rmsnorm, ops.rope
+    held = []
+
+    def rmsnorm(x, w, eps, **kw):
+        if id(w) not in gains:
+            return real_norm(x, w, eps, **kw)
+        held.append((w, eps))
+        return x
+
+    def rope(q, k, cos_sin, pos):
+        real_rope(q, k, cos_sin, pos)
+        (qw, eps), (kw, _) = held
+        del held[:]
+        D = q.shape[-1]
+        q.copy_(real_norm(q.reshape(-1, D), qw, eps).view_as(q))
+        k.copy_(real_norm(k.reshape(-1, D), kw, eps).view_as(k))
+    mp.setattr(ops, "rmsnorm", rmsnorm)
+    mp.setattr(ops, "rope", rope)
+
+
+Q_MUTANTS = [gains_swapped, k_norm_skipped, norm_after_rope]
+
+
+@pytest.mark.parametrize("fault", Q_MUTANTS, ids=lambda f: f.__name__)
+def test_qk_norm_mutant_is_noticed(fault, monkeypatch):
+    """Each fault of the QK-norm chain moves the worst row of b beyond 10x
+    the limit of Q, against the reference over the unchanged weights."""
+    from llm_d_inference_scheduler_amd import ops
+    ref_model = clean("Q", torch.bfloat16).worker.model
+    worst = ec.run("Q", "cpu", torch.bfloat16, ref_model=ref_model,
+                   setup=lambda w: fault(w, ops, monkeypatch)).worst
+    bound = 10 * ec.limit("Q")
+    print(f"MUTANT|Q|{fault.__name__}|b|{bound:.3e}|{worst['b']:.3e}|"
+          f"{worst['b'] / ec.limit('Q'):.1f}x")
+    assert worst["b"] > bound, (fault.__name__, worst)
+
+
+@pytest.mark.parametrize("mutant", MUTANTS, ids=lambda m: m.__name__)
+def test_mutant_is_noticed_under_qk_norm(mutant):
+    """The eight faults of scenario A, on scenario Q."""
+    worst = ec.run("Q", "cpu", torch.bfloat16, mutate=mutant()).worst
+    bound = 10 * ec.limit("Q")
+    print(f"MUTANT|Q|{mutant.__name__}|b|{bound:.3e}|{worst['b']:.3e}|"
+          f"{worst['b'] / ec.limit('Q'):.1f}x")
     assert worst["b"] > bound, (mutant.__name__, worst)
 
 
