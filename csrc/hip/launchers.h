@@ -146,6 +146,50 @@ hipError_t lds_lora_shrink(const LoraArgs& a, hipStream_t stream);
 // y[perm rows] += bf16(sum of partials) · B[slot]ᵀ
 hipError_t lds_lora_expand(const LoraArgs& a, hipStream_t stream);
 
+// ---- linear_fp8.hip ------------------------------------------------------
+
+// k a wave consumes per step: 16 weight bytes a lane, two MFMA K-steps.
+constexpr int LINEAR_FP8_KBLOCK = 64;
+// Output columns of one workgroup by rows (16, 32 and 64 are instantiated):
+// x comes from L2 once per column block, 2 * T / BN times the weight bytes,
+// so taller batches take the wider block. BN changes which workgroup sums
+// an element, never the order of its sum.
+constexpr int LINEAR_FP8_BN = 32;
+inline int linear_fp8_bn(int T) { return T <= 16 ? LINEAR_FP8_BN : 64; }
+// K is split across workgroups until a launch holds this many of them ...
+constexpr int LINEAR_FP8_SPLIT_WGS = 512;
+// ... while a split keeps at least this many k, 8 splits at the most.
+constexpr int LINEAR_FP8_SPLIT_MIN_K = 1024;
+
+// Workgroups along K of the fp8 linear kernel: a function of (in, out)
+// alone, so a row's bits do not depend on what else is launched.
+inline int linear_fp8_k_splits(int in, int out) {
+  const int wgs = (out + LINEAR_FP8_BN - 1) / LINEAR_FP8_BN;
+  int s = 1;
+  while (s < 8 && wgs * s < LINEAR_FP8_SPLIT_WGS &&
+         in / (2 * s) >= LINEAR_FP8_SPLIT_MIN_K)
+    s *= 2;
+  return s;
+}
+
+// y[m, n] = bf16(scale[n] * sum_k x[m, k] * float(wq[n, k])), fp32 sums.
+struct LinearFp8Args {
+  const void* x;        // [T, in] bf16, in % 64 == 0, 16-byte aligned
+  const void* wq;       // [out, in] OCP e4m3, out % 16 == 0, 16-byte aligned
+  const float* scale;   // [out]
+  void* y;              // [T, out] bf16
+  float* part;          // [n_split, T, out] fp32 scratch; unread if n_split 1
+  int T, in, out;
+  int n_split;          // linear_fp8_k_splits(in, out); 1 <= n_split
+  int bn;               // linear_fp8_bn(T); 16, 32 or 64
+};
+
+hipError_t lds_linear_fp8(const LinearFp8Args& a, hipStream_t stream);
+// W [in, out] bf16 = bf16(float(wq[n, k]) * scale[n]); in % 64 == 0,
+// out % 16 == 0, wq and W 16-byte aligned
+hipError_t lds_dequant_fp8_weight(const void* wq, const float* scale, void* W,
+                                  int in, int out, hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

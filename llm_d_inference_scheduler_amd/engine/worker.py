@@ -409,8 +409,14 @@ class EngineWorker:
                  kv_scale_headroom: float = 2.0,
                  kv_calib_tokens: int = 2048,
                  max_loras: int = 0,
-                 max_lora_rank: int = 16):
-        """kv_scales selects the per-head scales of an fp8 KV cache
+                 max_lora_rank: int = 16,
+                 weight_dtype: str = "auto"):
+        """weight_dtype "fp8" stores the four projections of every layer as
+        weight-only fp8 with one scale per output channel (DEVELOPMENT.md
+        "fp8 weights"); "auto" and "bf16" keep the runner's dtype. Both
+        ranks of a P/D pair must use the same value.
+
+        kv_scales selects the per-head scales of an fp8 KV cache
         (KVPool): "none" (unscaled direct cast), "calibrate" (run
         calibrate_kv_scales() at start-up) or the path of a scales JSON
         (KVPool.save_scales format). Calibration runs synthetic uniform
@@ -450,6 +456,7 @@ class EngineWorker:
         self.mgr = BlockManager(kv_blocks, self.pool.block_size,
                                 prefix_caching=prefix_caching)
         self.model = LlamaRunner(config, self.device, dtype, seed=seed)
+        self.model.quantize_weights(weight_dtype)
         self.seed = seed
         self.max_loras = max_loras
         self.adapters: Dict[str, LoraAdapter] = {}   # registered, on the host

@@ -147,12 +147,68 @@ class LlamaRunner:
         self.cos_sin = ops_ref.rope_table(c.max_position, c.head_dim,
                                           c.rope_theta, device=device)
 
+        # fp8 weights (quantize_weights): batches of up to this many rows
+        # go through ops.linear_fp8, larger ones through a dequantised bf16
+        # copy and torch.matmul (crossover: profiles/linear_fp8.md)
+        self.weight_dtype = "bf16"
+        self._fp8_kernel_max_t = 128
+        self._fp8_scratch: Dict[int, torch.Tensor] = {}
+
     def weight_bytes(self) -> int:
-        total = self.embed.numel() + self.lm_head.numel() + \
-            self.final_norm.numel()
+        tensors = [self.embed, self.lm_head, self.final_norm]
         for layer in self.layers:
-            total += sum(t.numel() for t in layer.values())
-        return total * self.embed.element_size()
+            for w in layer.values():
+                tensors.extend(w if isinstance(w, tuple) else (w,))
+        return sum(t.numel() * t.element_size() for t in tensors)
+
+    # ---- fp8 weights (DEVELOPMENT.md "fp8 weights") --------------------
+    def quantize_weights(self, weight_dtype: str) -> None:
+        """Convert the four projections of every layer in place to
+        weight-only fp8: layer[name] becomes the pair (wq [out, in]
+        float8_e4m3fn, scale [out] fp32) of ops.ref.quantize_weight_fp8.
+        Layer by layer, each bf16 tensor dropped as it is converted. The
+        embedding, lm_head and the norms keep the runner's dtype."""
+        if weight_dtype in ("auto", "bf16"):
+            return
+        if weight_dtype != "fp8":
+            raise ValueError(f"unknown weight_dtype {weight_dtype!r}")
+        if self.weight_dtype == "fp8":
+            return
+        if self.device.type == "cuda" and self.dtype != torch.bfloat16:
+            raise ValueError("fp8 weights on the GPU need a bf16 runner")
+        for layer in self.layers:
+            for name in LORA_TARGETS:
+                layer[name] = ops_ref.quantize_weight_fp8(layer[name])
+        self.weight_dtype = "fp8"
+
+    def dense_layers(self) -> List[Dict[str, torch.Tensor]]:
+        """self.layers with the four projections as fp32 [in, out] tensors,
+        an fp8 pair dequantised: the weights the forward pass applies."""
+        def dense(w):
+            if isinstance(w, tuple):
+                return (w[0].float() * w[1][:, None]).t()
+            return w.float()
+        return [{k: dense(w) if k in LORA_TARGETS else w
+                 for k, w in layer.items()} for layer in self.layers]
+
+    def _linear(self, x: torch.Tensor, w) -> torch.Tensor:
+        """x @ w for a projection of self.layers, dense or an fp8 pair."""
+        if not isinstance(w, tuple):
+            return x @ w
+        wq, scale = w
+        if not x.is_cuda or x.shape[0] <= self._fp8_kernel_max_t:
+            return ops.linear_fp8(x, wq, scale)
+        # one bf16 scratch per stream (prefill and decode may overlap),
+        # sized for the largest projection
+        key = torch.cuda.current_stream(x.device).cuda_stream
+        buf = self._fp8_scratch.get(key)
+        if buf is None:
+            n = max(p[0].numel() for layer in self.layers
+                    for p in layer.values() if isinstance(p, tuple))
+            buf = self._fp8_scratch[key] = torch.empty(
+                n, dtype=torch.bfloat16, device=x.device)
+        dense = buf[:wq.numel()].view(wq.shape[1], wq.shape[0])
+        return x @ ops.dequant_fp8_weight(wq, scale, dense)
 
     # ------------------------------------------------------------------
     def forward(self, batch: ForwardBatch, kv_pool: torch.Tensor,
@@ -199,7 +255,7 @@ class LlamaRunner:
             else:
                 normed = ops.rmsnorm(hidden, layer["input_norm"], c.rms_eps,
                                      residual=residual)
-            qkv = normed @ layer["wqkv"]
+            qkv = self._linear(normed, layer["wqkv"])
             if lora is not None:
                 lora_add(qkv, normed, li, "wqkv")
             T = qkv.shape[0]
@@ -246,16 +302,16 @@ class LlamaRunner:
                 attn = self._prefill_attention(batch, q, k_cache, v_cache,
                                                k_scale, v_scale)
             attn = attn.view(T, c.q_size)
-            o = attn @ layer["wo"]
+            o = self._linear(attn, layer["wo"])
             if lora is not None:
                 lora_add(o, attn, li, "wo")
             normed2 = ops.rmsnorm(o, layer["post_norm"], c.rms_eps,
                                   residual=residual)
-            gate_up = normed2 @ layer["wgate_up"]
+            gate_up = self._linear(normed2, layer["wgate_up"])
             if lora is not None:
                 lora_add(gate_up, normed2, li, "wgate_up")
             act = ops.silu_mul(gate_up)
-            hidden = act @ layer["wdown"]
+            hidden = self._linear(act, layer["wdown"])
             if lora is not None:
                 lora_add(hidden, act, li, "wdown")
         final = ops.rmsnorm(hidden, self.final_norm, c.rms_eps,

@@ -85,6 +85,9 @@ class NodeConfig:
     kv_blocks: Optional[int] = None
     kv_budget_bytes: int = 8 << 30
     kv_cache_dtype: str = "auto"    # auto|bf16|fp8 (fp8 = OCP e4m3 cache)
+    # auto|bf16|fp8 (fp8 = weight-only e4m3 projections, a scale per output
+    # channel); the same on every rank that exchanges KV
+    weight_dtype: str = "auto"
     # per-head scales of an fp8 cache (engine/worker.py): "none",
     # "calibrate" or the path of a scales JSON. Defaults from the
     # environment variable LLMD_KV_SCALES so a benchmark run can select
@@ -220,7 +223,8 @@ class NodeRunner:
             seed=cfg.seed, kv_scales=cfg.kv_scales,
             kv_scale_headroom=cfg.kv_scale_headroom,
             kv_calib_tokens=cfg.kv_calib_tokens,
-            max_loras=cfg.max_loras, max_lora_rank=cfg.max_lora_rank)
+            max_loras=cfg.max_loras, max_lora_rank=cfg.max_lora_rank,
+            weight_dtype=cfg.weight_dtype)
         if cfg.lora_adapters and cfg.max_loras <= 0:
             raise ValueError("lora_adapters needs max_loras >= 1")
         for name, spec in cfg.lora_adapters.items():

@@ -233,6 +233,27 @@ def lora_add(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
     ref.lora_add(y, x, A, B, perm, tiles)
 
 
+def linear_fp8(x: torch.Tensor, wq: torch.Tensor,
+               scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in] bf16 against a weight-only fp8 weight (DEVELOPMENT.md "fp8
+    weights"): wq [out, in] float8_e4m3fn and scale [out] fp32 from
+    ops.ref.quantize_weight_fp8 -> y [T, out], y[m, n] = scale[n] * sum_k
+    x[m, k] * float(wq[n, k]) with fp32 sums. in % 64 == 0, out % 16 == 0."""
+    if _use_hip(x):
+        return _ext.linear_fp8(x, wq, scale)
+    return ref.linear_fp8(x, wq, scale)
+
+
+def dequant_fp8_weight(wq: torch.Tensor, scale: torch.Tensor,
+                       out: torch.Tensor) -> torch.Tensor:
+    """Expand an fp8 weight into out [in, out] bf16, exactly
+    bf16(float(wq[n, k]) * scale[n]); returns out."""
+    if _use_hip(wq):
+        _ext.dequant_fp8_weight(wq, scale, out)
+        return out
+    return ref.dequant_fp8_weight(wq, scale, out)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

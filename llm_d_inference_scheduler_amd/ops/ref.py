@@ -690,6 +690,44 @@ def lora_add(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
         y[rows] = (y[rows].float() + tmp @ B[slot].float().T).to(y.dtype)
 
 
+# ---- fp8 weights (DEVELOPMENT.md "fp8 weights") ---------------------------
+
+FP8_E4M3_MAX = 448.0
+
+
+def quantize_weight_fp8(W: torch.Tensor):
+    """W [in, out], applied as x @ W -> (wq [out, in] float8_e4m3fn, scale
+    [out] fp32): scale[n] = absmax(W[:, n]) / 448 (1 for an all-zero column)
+    and wq[n, k] = W[k, n] / scale[n] rounded to e4m3. Plain torch on W's
+    device; fp32 division and round-to-nearest-even on either device, so a
+    CPU and a GPU worker hold the same bytes."""
+    wt = W.detach().float().t()
+    amax = wt.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    wq = (wt / scale[:, None]).clamp_(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return wq.to(torch.float8_e4m3fn).contiguous(), scale.contiguous()
+
+
+def dequant_fp8_weight(wq: torch.Tensor, scale: torch.Tensor,
+                       out: Optional[torch.Tensor] = None,
+                       dtype=torch.bfloat16) -> torch.Tensor:
+    """The dense [in, out] weight of an fp8 pair, float(wq[n, k]) * scale[n]
+    in fp32 rounded once to `dtype` (out's, if out is given and filled)."""
+    if out is not None:
+        dtype = out.dtype
+    W = (wq.float() * scale[:, None]).to(dtype).t()
+    if out is None:
+        return W.contiguous()
+    out.copy_(W)
+    return out
+
+
+def linear_fp8(x: torch.Tensor, wq: torch.Tensor,
+               scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in] against an fp8 weight -> [T, out] in x's dtype."""
+    return (x.float() @ (wq.float() * scale[:, None]).t()).to(x.dtype)
+
+
 _PREFIX_MODEL = PrefixModel()
 hash_prompts = _PREFIX_MODEL.hash_prompts
 table_update = _PREFIX_MODEL.table_update

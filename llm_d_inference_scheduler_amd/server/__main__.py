@@ -36,6 +36,10 @@ def parse_args(argv=None):
     p.add_argument("--kv-gb", type=float, default=160.0)
     p.add_argument("--kv-dtype", default="auto",
                    choices=["auto", "bf16", "fp8"])
+    p.add_argument("--weight-dtype", default="auto",
+                   choices=["auto", "bf16", "fp8"],
+                   help="fp8: weight-only e4m3 projections with one scale "
+                        "per output channel (half the weight bytes)")
     p.add_argument("--kv-scales", default=None,
                    help='per-head scales of an fp8 KV cache: "none", '
                         '"calibrate" (synthetic tokens at start-up) or the '
@@ -99,7 +103,7 @@ def build_node(args):
         dtype=torch.bfloat16 if use_gpu else torch.float32,
         kv_blocks=None if use_gpu else 2048,
         kv_budget_bytes=int(args.kv_gb * (1 << 30)),
-        kv_cache_dtype=args.kv_dtype,
+        kv_cache_dtype=args.kv_dtype, weight_dtype=args.weight_dtype,
         flow_control=args.flow_control,
         decode_chunk_tokens=args.decode_chunk_tokens or None,
         seed=args.seed, max_loras=args.max_loras,

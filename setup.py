@@ -40,6 +40,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/flash_prefill_glds.hip",
         "csrc/hip/sampler.hip",
         "csrc/hip/lora.hip",
+        "csrc/hip/linear_fp8.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],
