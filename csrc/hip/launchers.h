@@ -190,6 +190,51 @@ hipError_t lds_linear_fp8(const LinearFp8Args& a, hipStream_t stream);
 hipError_t lds_dequant_fp8_weight(const void* wq, const float* scale, void* W,
                                   int in, int out, hipStream_t stream);
 
+// ---- linear_mxfp4.hip ----------------------------------------------------
+
+// k a wave consumes per step: one 32-wide MX group a lane group, four MFMAs.
+constexpr int LINEAR_MXFP4_KBLOCK = 128;
+// Output columns of one workgroup by rows (16, 32 and 64 are instantiated),
+// as for fp8: BN changes which workgroup sums an element, never the order.
+constexpr int LINEAR_MXFP4_BN = 32;
+inline int linear_mxfp4_bn(int T) { return T <= 16 ? LINEAR_MXFP4_BN : 64; }
+// K is split across workgroups until a launch holds this many of them ...
+constexpr int LINEAR_MXFP4_SPLIT_WGS = 512;
+// ... while a split keeps at least this many k (16 K blocks, four a wave),
+// 8 splits at the most.
+constexpr int LINEAR_MXFP4_SPLIT_MIN_K = 2048;
+
+// Workgroups along K of the mxfp4 linear kernel: a function of (in, out)
+// alone, so a row's bits do not depend on what else is launched.
+inline int linear_mxfp4_k_splits(int in, int out) {
+  const int wgs = (out + LINEAR_MXFP4_BN - 1) / LINEAR_MXFP4_BN;
+  int s = 1;
+  while (s < 8 && wgs * s < LINEAR_MXFP4_SPLIT_WGS &&
+         in / (2 * s) >= LINEAR_MXFP4_SPLIT_MIN_K)
+    s *= 2;
+  return s;
+}
+
+// y[m, n] = bf16(sum_k x[m, k] * e2m1(wq[n, k]) * 2^(scale[n, k/32] - 127)),
+// fp32 sums.
+struct LinearMxfp4Args {
+  const void* x;        // [T, in] bf16, in % 128 == 0, 16-byte aligned
+  const void* wq;       // [out, in / 2] uint8, out % 16 == 0, 16-byte aligned
+  const void* scale;    // [out, in / 32] uint8 (e8m0)
+  void* y;              // [T, out] bf16
+  float* part;          // [n_split, T, out] fp32 scratch; unread if n_split 1
+  int T, in, out;
+  int n_split;          // linear_mxfp4_k_splits(in, out); 1 <= n_split
+  int bn;               // linear_mxfp4_bn(T); 16, 32 or 64
+};
+
+hipError_t lds_linear_mxfp4(const LinearMxfp4Args& a, hipStream_t stream);
+// W [in, out] bf16 = e2m1(wq[n, k]) * 2^(scale[n, k/32] - 127), exact;
+// in % 128 == 0, out % 16 == 0, wq and W 16-byte aligned
+hipError_t lds_dequant_mxfp4_weight(const void* wq, const void* scale,
+                                    void* W, int in, int out,
+                                    hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

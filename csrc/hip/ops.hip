@@ -696,6 +696,80 @@ void dequant_fp8_weight(torch::Tensor wq, torch::Tensor scale,
                                    out.data_ptr(), in, n_out, cur_stream()));
 }
 
+// ---- mxfp4 weights ----
+
+// The (wq, scale) pair of an MXFP4 weight (DEVELOPMENT.md "MXFP4 weights"),
+// anchored on `anchor`: wq [out, in / 2] uint8 with in % 128 == 0,
+// out % 16 == 0, 16-byte aligned; scale [out, in / 32] uint8 (read by the
+// byte, so any alignment).
+void check_mxfp4_weight(const torch::Tensor& wq, const torch::Tensor& scale,
+                        const torch::Tensor& anchor,
+                        const char* anchor_name) {
+  check_tensor(wq, "wq", anchor, anchor_name, at::kByte, {ANY, ANY});
+  TORCH_CHECK((wq.size(1) * 2) % LINEAR_MXFP4_KBLOCK == 0, "2 * wq.size(1) "
+              "must be a multiple of ", LINEAR_MXFP4_KBLOCK, ", got ",
+              wq.size(1) * 2);
+  TORCH_CHECK(wq.size(0) % 16 == 0, "wq.size(0) must be a multiple of 16, "
+              "got ", wq.size(0));
+  check_tensor(scale, "scale", anchor, anchor_name, at::kByte,
+               {wq.size(0), wq.size(1) / 16});
+  check_aligned16(wq, "wq");
+}
+
+// y = bf16(x · dequant(wq, scale)) with fp32 sums: x [T, in] bf16 against an
+// MXFP4 weight. bn and k_splits are the launch geometry, for measurement
+// only (tools/linear_fp8_bench.py): 0 is what serves (linear_mxfp4_bn,
+// linear_mxfp4_k_splits) and what ops.linear_mxfp4 always passes. A k_splits
+// other than 0 changes the order of the sums: the guarantee that a row's
+// bits depend on (in, out) alone holds for k_splits = 0 only.
+torch::Tensor linear_mxfp4(torch::Tensor x, torch::Tensor wq,
+                           torch::Tensor scale, int64_t bn,
+                           int64_t k_splits) {
+  check_tensor(x, "x", x, "x", at::kBFloat16, {ANY, ANY});
+  check_mxfp4_weight(wq, scale, x, "x");
+  TORCH_CHECK(x.size(1) == wq.size(1) * 2, "x.size(1) (", x.size(1),
+              ") must be 2 * wq.size(1) (", wq.size(1) * 2, ")");
+  check_aligned16(x, "x");
+  TORCH_CHECK(bn == 0 || bn == 16 || bn == 32 || bn == 64, "bn must be 0, "
+              "16, 32 or 64, got ", bn);
+  LinearMxfp4Args a{};
+  a.T = check_int(x.size(0), 0, GRID_YZ_MAX * 32, "x.size(0)");
+  a.in = check_int(x.size(1), 0, INT_MAX, "x.size(1)");
+  a.out = check_int(wq.size(0), 0, INT_MAX, "wq.size(0)");
+  a.bn = bn ? (int)bn : linear_mxfp4_bn(a.T);
+  a.n_split = check_int(k_splits, 0, 64, "k_splits");
+  if (a.n_split == 0) a.n_split = linear_mxfp4_k_splits(a.in, a.out);
+  auto y = torch::empty({a.T, a.out}, x.options());
+  if (a.T == 0 || a.out == 0) return y;
+  torch::Tensor part;
+  if (a.n_split > 1) {
+    part = torch::empty({a.n_split, a.T, a.out},
+                        x.options().dtype(torch::kFloat32));
+    a.part = part.data_ptr<float>();
+  }
+  a.x = x.data_ptr();
+  a.wq = wq.data_ptr();
+  a.scale = scale.data_ptr();
+  a.y = y.data_ptr();
+  CHECK_HIP(lds_linear_mxfp4(a, cur_stream()));
+  return y;
+}
+
+// out [in, out] bf16 = e2m1(wq[n, k]) * 2^(scale[n, k / 32] - 127), exact:
+// the dense weight torch.matmul reads at prefill-sized batches.
+void dequant_mxfp4_weight(torch::Tensor wq, torch::Tensor scale,
+                          torch::Tensor out) {
+  check_mxfp4_weight(wq, scale, wq, "wq");
+  check_tensor(out, "out", wq, "wq", at::kBFloat16,
+               {wq.size(1) * 2, wq.size(0)});
+  check_aligned16(out, "out");
+  const int in = check_int(wq.size(1) * 2, 0, INT_MAX, "2 * wq.size(1)");
+  const int n_out = check_int(wq.size(0), 0, GRID_YZ_MAX * 64, "wq.size(0)");
+  CHECK_HIP(lds_dequant_mxfp4_weight(wq.data_ptr(), scale.data_ptr(),
+                                     out.data_ptr(), in, n_out,
+                                     cur_stream()));
+}
+
 // ---- sampler ----
 
 // One per-row parameter vector of sample(): [B], on the logits' device.
@@ -932,6 +1006,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bn") = 0, py::arg("k_splits") = 0);
   m.def("dequant_fp8_weight", &dequant_fp8_weight,
         "expand an fp8 weight into out [in, out] bf16",
+        py::arg("wq"), py::arg("scale"), py::arg("out"));
+  m.def("linear_mxfp4", &linear_mxfp4,
+        "x [T, in] bf16 against an MXFP4 weight (wq [out, in / 2] uint8, "
+        "scale [out, in / 32] uint8 e8m0) -> y [T, out] bf16; bn, k_splits: "
+        "measurement knobs, a k_splits other than 0 voids the "
+        "bit-invariance of rows",
+        py::arg("x"), py::arg("wq"), py::arg("scale"),
+        py::arg("bn") = 0, py::arg("k_splits") = 0);
+  m.def("dequant_mxfp4_weight", &dequant_mxfp4_weight,
+        "expand an MXFP4 weight into out [in, out] bf16",
         py::arg("wq"), py::arg("scale"), py::arg("out"));
   m.def("sample", &sample,
         "fused temperature/top-k/top-p/seeded sampler with logprobs -> "

@@ -147,11 +147,13 @@ class LlamaRunner:
         self.cos_sin = ops_ref.rope_table(c.max_position, c.head_dim,
                                           c.rope_theta, device=device)
 
-        # fp8 weights (quantize_weights): batches of up to this many rows
-        # go through ops.linear_fp8, larger ones through a dequantised bf16
-        # copy and torch.matmul (crossover: profiles/linear_fp8.md)
+        # quantised weights (quantize_weights): batches of up to this many
+        # rows go through ops.linear_fp8 / ops.linear_mxfp4, larger ones
+        # through a dequantised bf16 copy and torch.matmul (crossovers:
+        # profiles/linear_fp8.md, profiles/linear_mxfp4.md)
         self.weight_dtype = "bf16"
         self._fp8_kernel_max_t = 128
+        self._mxfp4_kernel_max_t = 128
         self._fp8_scratch: Dict[int, torch.Tensor] = {}
 
     def weight_bytes(self) -> int:
@@ -161,53 +163,74 @@ class LlamaRunner:
                 tensors.extend(w if isinstance(w, tuple) else (w,))
         return sum(t.numel() * t.element_size() for t in tensors)
 
-    # ---- fp8 weights (DEVELOPMENT.md "fp8 weights") --------------------
+    # ---- quantised weights (DEVELOPMENT.md "fp8 weights", "MXFP4 weights")
     def quantize_weights(self, weight_dtype: str) -> None:
-        """Convert the four projections of every layer in place to
-        weight-only fp8: layer[name] becomes the pair (wq [out, in]
-        float8_e4m3fn, scale [out] fp32) of ops.ref.quantize_weight_fp8.
-        Layer by layer, each bf16 tensor dropped as it is converted. The
-        embedding, lm_head and the norms keep the runner's dtype."""
+        """Convert the four projections of every layer in place to a
+        weight-only format. "fp8": layer[name] becomes the pair (wq
+        [out, in] float8_e4m3fn, scale [out] fp32) of
+        ops.ref.quantize_weight_fp8. "mxfp4": the pair (wq [out, in / 2]
+        uint8, scale [out, in / 32] uint8) of ops.ref.quantize_weight_mxfp4;
+        the two are told apart by wq's dtype. Layer by layer, each bf16
+        tensor dropped as it is converted. The embedding, lm_head and the
+        norms keep the runner's dtype. A quantised runner cannot be
+        converted to another format: the bf16 weights are gone."""
         if weight_dtype in ("auto", "bf16"):
             return
-        if weight_dtype != "fp8":
+        if weight_dtype not in ("fp8", "mxfp4"):
             raise ValueError(f"unknown weight_dtype {weight_dtype!r}")
-        if self.weight_dtype == "fp8":
+        if self.weight_dtype == weight_dtype:
             return
+        if self.weight_dtype != "bf16":
+            raise ValueError(f"weights are already {self.weight_dtype}, "
+                             f"cannot convert them to {weight_dtype}")
         if self.device.type == "cuda" and self.dtype != torch.bfloat16:
-            raise ValueError("fp8 weights on the GPU need a bf16 runner")
+            raise ValueError(f"{weight_dtype} weights on the GPU need a bf16 "
+                             "runner")
+        quantize = ops_ref.quantize_weight_fp8 if weight_dtype == "fp8" \
+            else ops_ref.quantize_weight_mxfp4
         for layer in self.layers:
             for name in LORA_TARGETS:
-                layer[name] = ops_ref.quantize_weight_fp8(layer[name])
-        self.weight_dtype = "fp8"
+                layer[name] = quantize(layer[name])
+        self.weight_dtype = weight_dtype
 
     def dense_layers(self) -> List[Dict[str, torch.Tensor]]:
         """self.layers with the four projections as fp32 [in, out] tensors,
-        an fp8 pair dequantised: the weights the forward pass applies."""
+        an fp8 or mxfp4 pair dequantised exactly: the weights the forward
+        pass applies."""
         def dense(w):
-            if isinstance(w, tuple):
-                return (w[0].float() * w[1][:, None]).t()
-            return w.float()
+            if not isinstance(w, tuple):
+                return w.float()
+            if w[0].dtype == torch.uint8:
+                return ops_ref.dequant_mxfp4_weight(*w, dtype=torch.float32)
+            return (w[0].float() * w[1][:, None]).t()
         return [{k: dense(w) if k in LORA_TARGETS else w
                  for k, w in layer.items()} for layer in self.layers]
 
     def _linear(self, x: torch.Tensor, w) -> torch.Tensor:
-        """x @ w for a projection of self.layers, dense or an fp8 pair."""
+        """x @ w for a projection of self.layers: dense, an fp8 pair or an
+        mxfp4 pair (wq is uint8)."""
         if not isinstance(w, tuple):
             return x @ w
         wq, scale = w
-        if not x.is_cuda or x.shape[0] <= self._fp8_kernel_max_t:
-            return ops.linear_fp8(x, wq, scale)
+        mx = wq.dtype == torch.uint8
+        max_t = self._mxfp4_kernel_max_t if mx else self._fp8_kernel_max_t
+        if not x.is_cuda or x.shape[0] <= max_t:
+            return ops.linear_mxfp4(x, wq, scale) if mx else \
+                ops.linear_fp8(x, wq, scale)
         # one bf16 scratch per stream (prefill and decode may overlap),
-        # sized for the largest projection
+        # sized for the largest projection: in * out elements, which is
+        # twice wq.numel() for mxfp4
         key = torch.cuda.current_stream(x.device).cuda_stream
         buf = self._fp8_scratch.get(key)
         if buf is None:
             n = max(p[0].numel() for layer in self.layers
                     for p in layer.values() if isinstance(p, tuple))
             buf = self._fp8_scratch[key] = torch.empty(
-                n, dtype=torch.bfloat16, device=x.device)
-        dense = buf[:wq.numel()].view(wq.shape[1], wq.shape[0])
+                2 * n if mx else n, dtype=torch.bfloat16, device=x.device)
+        n_out, n_in = wq.shape[0], x.shape[1]
+        dense = buf[:n_in * n_out].view(n_in, n_out)
+        if mx:
+            return x @ ops.dequant_mxfp4_weight(wq, scale, dense)
         return x @ ops.dequant_fp8_weight(wq, scale, dense)
 
     # ------------------------------------------------------------------

@@ -254,6 +254,28 @@ def dequant_fp8_weight(wq: torch.Tensor, scale: torch.Tensor,
     return ref.dequant_fp8_weight(wq, scale, out)
 
 
+def linear_mxfp4(x: torch.Tensor, wq: torch.Tensor,
+                 scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in] bf16 against an MXFP4 weight (DEVELOPMENT.md "MXFP4
+    weights"): wq [out, in / 2] uint8 (two e2m1 codes a byte) and scale
+    [out, in / 32] uint8 (e8m0) from ops.ref.quantize_weight_mxfp4 -> y
+    [T, out], y[m, n] = sum_k x[m, k] * e2m1(wq[n, k]) * 2^(scale[n, k / 32]
+    - 127) with fp32 sums. in % 128 == 0, out % 16 == 0."""
+    if _use_hip(x):
+        return _ext.linear_mxfp4(x, wq, scale)
+    return ref.linear_mxfp4(x, wq, scale)
+
+
+def dequant_mxfp4_weight(wq: torch.Tensor, scale: torch.Tensor,
+                         out: torch.Tensor) -> torch.Tensor:
+    """Expand an MXFP4 weight into out [in, out] bf16, exactly; returns
+    out."""
+    if _use_hip(wq):
+        _ext.dequant_mxfp4_weight(wq, scale, out)
+        return out
+    return ref.dequant_mxfp4_weight(wq, scale, out)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

@@ -728,6 +728,78 @@ def linear_fp8(x: torch.Tensor, wq: torch.Tensor,
     return (x.float() @ (wq.float() * scale[:, None]).t()).to(x.dtype)
 
 
+# ---- MXFP4 weights (DEVELOPMENT.md "MXFP4 weights") -----------------------
+
+MXFP4_GROUP = 32
+# the magnitudes of the e2m1 codes 0..7; bit 3 of a code is the sign
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _exp2_f32(biased: torch.Tensor) -> torch.Tensor:
+    """2^(biased - 127) in fp32 for integer biased in [1, 254]: the value is
+    placed in the exponent field, so the power is exact on any device."""
+    return (biased.to(torch.int32) << 23).view(torch.float32)
+
+
+def quantize_weight_mxfp4(W: torch.Tensor):
+    """W [in, out], applied as x @ W -> (wq [out, in / 2] uint8, scale
+    [out, in / 32] uint8), OCP Microscaling FP4. Group g of row n covers
+    k in [32g, 32g + 32) and shares the exponent X = floor(log2(absmax)) - 2,
+    stored as e8m0 X + 127 clamped to [2, 252] (127 for an all-zero group).
+    Elements are W[k, n] / 2^X rounded to the nearest e2m1 value, ties to the
+    even code, saturating at 6; byte j of a row holds k = 2j in its low
+    nibble and k = 2j + 1 in its high nibble. Plain torch on W's device; the
+    exponent comes from frexp and the power of two from bits, so a CPU and a
+    GPU worker hold the same bytes. in % 32 == 0."""
+    wt = W.detach().float().t().contiguous()
+    n_out, n_in = wt.shape
+    grp = wt.view(n_out, n_in // MXFP4_GROUP, MXFP4_GROUP)
+    amax = grp.abs().amax(dim=2)
+    # amax = m * 2^e with m in [0.5, 1): floor(log2(amax)) = e - 1
+    _, e = torch.frexp(amax)
+    biased = torch.where(amax > 0, (e - 3 + 127).clamp(2, 252),
+                         torch.full_like(e, 127))
+    a = (grp * _exp2_f32(254 - biased)[:, :, None]).abs()
+    # midpoints between neighbouring values; a tie goes to the even code
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) +
+            (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    # the sign survives rounding to zero (code 8 is -0), as in a hardware cast
+    code = (code + 8 * (grp < 0)).to(torch.uint8)
+    code = code.view(n_out, n_in // 2, 2)
+    wq = code[:, :, 0] | (code[:, :, 1] << 4)
+    return wq.contiguous(), biased.to(torch.uint8).contiguous()
+
+
+def _mxfp4_dense_f32(wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """[out, in] fp32, exact: e2m1(code) * 2^(scale - 127)."""
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES),
+                       dtype=torch.float32, device=wq.device)
+    codes = torch.stack((wq & 15, wq >> 4), dim=2).view(wq.shape[0], -1)
+    sc = _exp2_f32(scale).repeat_interleave(MXFP4_GROUP, dim=1)
+    return lut[codes.long()] * sc
+
+
+def dequant_mxfp4_weight(wq: torch.Tensor, scale: torch.Tensor,
+                         out: Optional[torch.Tensor] = None,
+                         dtype=torch.bfloat16) -> torch.Tensor:
+    """The dense [in, out] weight of an MXFP4 pair in `dtype` (out's, if out
+    is given and filled). Every value is zero or a normal bf16, so bf16 and
+    wider types hold it exactly."""
+    if out is not None:
+        dtype = out.dtype
+    W = _mxfp4_dense_f32(wq, scale).to(dtype).t()
+    if out is None:
+        return W.contiguous()
+    out.copy_(W)
+    return out
+
+
+def linear_mxfp4(x: torch.Tensor, wq: torch.Tensor,
+                 scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in] against an MXFP4 weight -> [T, out] in x's dtype."""
+    return (x.float() @ _mxfp4_dense_f32(wq, scale).t()).to(x.dtype)
+
+
 _PREFIX_MODEL = PrefixModel()
 hash_prompts = _PREFIX_MODEL.hash_prompts
 table_update = _PREFIX_MODEL.table_update

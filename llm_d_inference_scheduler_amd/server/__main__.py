@@ -37,9 +37,11 @@ def parse_args(argv=None):
     p.add_argument("--kv-dtype", default="auto",
                    choices=["auto", "bf16", "fp8"])
     p.add_argument("--weight-dtype", default="auto",
-                   choices=["auto", "bf16", "fp8"],
+                   choices=["auto", "bf16", "fp8", "mxfp4"],
                    help="fp8: weight-only e4m3 projections with one scale "
-                        "per output channel (half the weight bytes)")
+                        "per output channel (half the weight bytes); mxfp4: "
+                        "OCP Microscaling FP4 projections, e2m1 with one "
+                        "e8m0 exponent per 32 values (17/64 of the bytes)")
     p.add_argument("--kv-scales", default=None,
                    help='per-head scales of an fp8 KV cache: "none", '
                         '"calibrate" (synthetic tokens at start-up) or the '

@@ -1,7 +1,8 @@
 """Microbench of the fp8-weights linear against the bf16 GEMM it replaces
 (results: profiles/linear_fp8.md).
 
-    python tools/linear_fp8_bench.py [--rounds 9] [--geometry]
+    python tools/linear_fp8_bench.py [--format fp8|mxfp4] [--rounds 9]
+                                     [--geometry]
 
 Shapes: the four projections of Llama-3-8B and of Qwen3-32B, for T in
 {1, 8, 16, 32, 64, 128, 256}. Arms, timed in one process in interleaved
@@ -24,6 +25,11 @@ the float64 product under the bound of tests/test_gpu_linear_fp8.py, at
 every geometry that is timed.
 Reported per arm: the median per-call time over the rounds, in us; `floor` is
 the weight bytes (fp8) over 8 TB/s.
+--format mxfp4 (results: profiles/linear_mxfp4.md) times ops.linear_mxfp4 and
+ops.dequant_mxfp4_weight + matmul as `kernel` and `dequant` instead, for T in
+{1, 4, 16, 32, 64, 128, 256}, keeps the fp8 kernel as the arm `fp8` in the
+same rounds, and adds `<arm>_spread`, the largest minus the smallest round of
+an arm; `floor` then counts the codes and the scale bytes.
 """
 import argparse
 import json
@@ -43,6 +49,7 @@ from llm_d_inference_scheduler_amd.models.llama import (  # noqa: E402
 
 DEV = "cuda"
 TS = (1, 8, 16, 32, 64, 128, 256)
+TS_MXFP4 = (1, 4, 16, 32, 64, 128, 256)
 WINDOW_US = 10000.0
 COLD_BYTES = 512 << 20
 HBM_BYTES_PER_US = 8e6
@@ -66,7 +73,7 @@ def time_arm(fn, iters):
     return start.elapsed_time(end) * 1e3 / iters          # us per call
 
 
-def bench(fns, rounds):
+def bench(fns, rounds, spread=False):
     names = list(fns)
     for fn in fns.values():                                # warm-up
         for _ in range(3):
@@ -78,7 +85,11 @@ def bench(fns, rounds):
     for r in range(rounds):
         for n in names[r % len(names):] + names[:r % len(names)]:
             times[n].append(time_arm(fns[n], iters[n]))
-    return {n: round(statistics.median(ts), 2) for n, ts in times.items()}
+    res = {n: round(statistics.median(ts), 2) for n, ts in times.items()}
+    if spread:
+        res.update({n + "_spread": round(max(ts) - min(ts), 2)
+                    for n, ts in times.items()})
+    return res
 
 
 def rotating(fn, n):
@@ -91,16 +102,17 @@ def rotating(fn, n):
     return call
 
 
-def check(y, x, wq, scale, what):
+def check(y, x, wq, scale, what, mx=False):
     """y against the float64 product, first 8 rows, under the tests' bound
     (bf16 rounding of y plus fp32 accumulation in any order, doubled; the
     dequant arm also rounds the weight and sums in bf16 GEMM order, which
     the 2^-7 |x||w| term covers)."""
     n = min(8, x.shape[0])
-    w64 = wq.double() * scale.double()[:, None]
+    w64 = ops.ref.dequant_mxfp4_weight(wq, scale, dtype=torch.float64) \
+        if mx else (wq.double() * scale.double()[:, None]).t()
     x64 = x[:n].double()
-    y64 = x64 @ w64.t()
-    mag = x64.abs() @ w64.abs().t()
+    y64 = x64 @ w64
+    mag = x64.abs() @ w64.abs()
     slack = 2.0 ** -7 if what == "dequant" else x.shape[1] * 2.0 ** -23
     bad = (y[:n].double() - y64).abs() > 2.0 ** -8 * y64.abs() + slack * mag
     if bool(bad.any()):
@@ -109,11 +121,16 @@ def check(y, x, wq, scale, what):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--format", choices=["fp8", "mxfp4"], default="fp8")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--geometry", action="store_true")
     ap.add_argument("--warm", action="store_true")
     args = ap.parse_args()
     ext = ops.hip_ops()
+    mx = args.format == "mxfp4"
+    linear, dequant = (ops.linear_mxfp4, ops.dequant_mxfp4_weight) if mx \
+        else (ops.linear_fp8, ops.dequant_fp8_weight)
+    ext_linear = ext.linear_mxfp4 if mx else ext.linear_fp8
     _load_tuned_gemms()     # the bf16 arm runs the GEMMs the runner runs
     gen = torch.Generator().manual_seed(0)
     geometries = [(bn, s) for bn in (16, 32, 64) for s in (1, 2, 4, 8)]
@@ -121,44 +138,53 @@ def main():
         for proj, (n_in, n_out) in projections(c).items():
             W = (torch.randn(n_in, n_out, generator=gen) * 0.02) \
                 .to(torch.bfloat16).to(DEV)
-            wq, scale = ops.ref.quantize_weight_fp8(W)
+            wq, scale = ops.ref.quantize_weight_mxfp4(W) if mx else \
+                ops.ref.quantize_weight_fp8(W)
             dense = torch.empty_like(W)
             n8 = 1 if args.warm else -(-COLD_BYTES // wq.numel())
+            if mx and not args.geometry:       # the fp8 arm of the same run
+                wq8, scale8 = ops.ref.quantize_weight_fp8(W)
+                m8 = 1 if args.warm else -(-COLD_BYTES // wq8.numel())
+                wq8s = [wq8] + [wq8.clone() for _ in range(m8 - 1)]
             n16 = 1 if args.warm or args.geometry else \
                 -(-COLD_BYTES // (2 * W.numel()))
             wqs = [wq] + [wq.clone() for _ in range(n8 - 1)]
             Ws = [W] + [W.clone() for _ in range(n16 - 1)]
-            for T in TS:
+            for T in TS_MXFP4 if mx else TS:
                 if args.geometry and T not in (1, 16, 32, 64):
                     continue
                 x = torch.randn(T, n_in, generator=gen).to(torch.bfloat16) \
                     .to(DEV)
                 if args.geometry:
                     for bn, s in geometries:
-                        check(ext.linear_fp8(x, wq, scale, bn, s), x, wq,
-                              scale, f"bn{bn}_s{s}")
+                        check(ext_linear(x, wq, scale, bn, s), x, wq,
+                              scale, f"bn{bn}_s{s}", mx)
                     fns = {f"bn{bn}_s{s}": rotating(
-                        lambda i, bn=bn, s=s: ext.linear_fp8(
+                        lambda i, bn=bn, s=s: ext_linear(
                             x, wqs[i], scale, bn, s), n8)
                         for bn, s in geometries}
                 else:
-                    check(ops.linear_fp8(x, wq, scale), x, wq, scale,
-                          "kernel")
-                    check(x @ ops.dequant_fp8_weight(wq, scale, dense), x,
-                          wq, scale, "dequant")
+                    check(linear(x, wq, scale), x, wq, scale, "kernel", mx)
+                    check(x @ dequant(wq, scale, dense), x, wq, scale,
+                          "dequant", mx)
                     fns = {
-                        "kernel": rotating(lambda i: ops.linear_fp8(
+                        "kernel": rotating(lambda i: linear(
                             x, wqs[i], scale), n8),
                         "dequant": rotating(
-                            lambda i: x @ ops.dequant_fp8_weight(
-                                wqs[i], scale, dense), n8),
+                            lambda i: x @ dequant(wqs[i], scale, dense), n8),
                         "bf16": rotating(lambda i: x @ Ws[i], n16)}
+                    if mx:
+                        fns["fp8"] = rotating(lambda i: ops.linear_fp8(
+                            x, wq8s[i], scale8), m8)
                 print(json.dumps(dict(
                     model=c.name, proj=proj, n_in=n_in, n_out=n_out, T=T,
-                    copies=n8, floor=round(n_in * n_out / HBM_BYTES_PER_US,
-                                           2),
-                    **bench(fns, args.rounds))), flush=True)
+                    copies=n8, floor=round(
+                        (wq.numel() + (scale.numel() if mx else 0))
+                        / HBM_BYTES_PER_US, 2),
+                    **bench(fns, args.rounds, spread=mx))), flush=True)
             del W, wq, scale, dense, wqs, Ws
+            if mx and not args.geometry:
+                del wq8, scale8, wq8s
             torch.cuda.empty_cache()
 
 
