@@ -235,6 +235,64 @@ hipError_t lds_dequant_mxfp4_weight(const void* wq, const void* scale,
                                     void* W, int in, int out,
                                     hipStream_t stream);
 
+// ---- moe.hip -------------------------------------------------------------
+
+constexpr int MOE_MAX_EXPERTS = 256;
+constexpr int MOE_MAX_TOPK = 8;
+// Tokens of one routing workgroup (one MFMA row block).
+constexpr int MOE_ROUTE_TOKENS = 16;
+
+// ids[t, :] = the k experts with the largest router logits (value descending,
+// ties to the lower index); w[t, :] = their softmax over all E, divided by
+// their sum with renorm.
+struct MoeRouteArgs {
+  const void* x;        // [T, H] bf16, H % 32 == 0, 16-byte aligned
+  const void* router;   // [E, H] bf16, 16-byte aligned
+  int32_t* ids;         // [T, k]
+  float* w;             // [T, k]
+  int T, H;
+  int E;                // 1 .. MOE_MAX_EXPERTS
+  int k;                // 1 .. min(MOE_MAX_TOPK, E)
+  int renorm;
+};
+
+hipError_t lds_moe_route(const MoeRouteArgs& a, hipStream_t stream);
+
+// Row blocks of a work-list tile, from the mean rows per expert alone:
+// tiles are TM = 16 * MB rows tall. MB changes which workgroup computes a
+// pair, never the order of its sums.
+inline int moe_mb(int64_t P, int E) {
+  const int64_t per = P / E;
+  return per <= 16 ? 1 : per <= 32 ? 2 : 4;
+}
+// Tiles a work list can hold: an expert with c pairs takes ceil(c / TM).
+inline int64_t moe_tile_bound(int64_t P, int E, int mb) {
+  return P / (16 * mb) + (P < E ? P : E);
+}
+
+// y[t] = bf16(sum_j w[t, j] * (bf16(silu(x[t] Wg_e) * (x[t] Wu_e)) W2_e)),
+// e = ids[t, j], fp32 sums, j in slot order. P = T * k (token, slot) pairs.
+// An id outside [0, E) is read as the nearest expert: nothing is checked on
+// the device, and nothing goes out of bounds.
+struct MoeFfnArgs {
+  const void* x;        // [T, H] bf16, H % 32 == 0, 16-byte aligned
+  const void* w13;      // [E, 2 I, H] bf16: gate rows, then up rows
+  const void* w2;       // [E, H, I] bf16, I % 16 == 0
+  const int32_t* ids;   // [T, k]
+  const float* w;       // [T, k]
+  void* y;              // [T, H] bf16
+  // scratch, every pointer 16-byte aligned
+  void* act;            // [moe_tile_bound * TM, I] bf16, by sorted position
+  float* y2;            // [P, H] fp32, by pair
+  int32_t* tiles;       // [moe_tile_bound, 3] start, count <= TM, expert
+  int32_t* n_tiles;     // [1]
+  int32_t* perm;        // [moe_tile_bound * TM] sorted position -> pair
+  int T, H, I, E, k;
+  int mb;               // moe_mb(T * k, E)
+};
+
+hipError_t lds_moe_ffn(const MoeFfnArgs& a, hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

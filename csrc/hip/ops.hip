@@ -770,6 +770,127 @@ void dequant_mxfp4_weight(torch::Tensor wq, torch::Tensor scale,
                                      cur_stream()));
 }
 
+// ---- mixture of experts ----
+
+// x [T, H] bf16 of a MoE op (DEVELOPMENT.md "Mixture of experts"): H % 32
+// == 0, 16-byte aligned. Returns T.
+int check_moe_x(const torch::Tensor& x) {
+  check_tensor(x, "x", x, "x", at::kBFloat16, {ANY, ANY});
+  TORCH_CHECK(x.size(1) % 32 == 0 && x.size(1) >= 32, "x.size(1) must be a "
+              "positive multiple of 32, got ", x.size(1));
+  check_int(x.size(1), 32, INT_MAX, "x.size(1)");
+  check_aligned16(x, "x");
+  return check_int(x.size(0), 0, INT_MAX / MOE_MAX_TOPK, "x.size(0)");
+}
+
+// (ids [T, k] int32, w [T, k] fp32) = the k largest of softmax(x · routerᵀ)
+// per token, value descending, ties to the lower index; with renorm divided
+// by their sum.
+std::vector<torch::Tensor> moe_route(torch::Tensor x, torch::Tensor router,
+                                     int64_t k, bool renorm) {
+  MoeRouteArgs a{};
+  a.T = check_moe_x(x);
+  a.H = (int)x.size(1);
+  check_tensor(router, "router", x, "x", at::kBFloat16, {ANY, x.size(1)});
+  check_aligned16(router, "router");
+  a.E = check_int(router.size(0), 1, MOE_MAX_EXPERTS, "router.size(0)");
+  a.k = check_int(k, 1, std::min<int64_t>(MOE_MAX_TOPK, a.E), "k");
+  a.renorm = renorm;
+  auto ids = torch::empty({a.T, k}, x.options().dtype(torch::kInt32));
+  auto w = torch::empty({a.T, k}, x.options().dtype(torch::kFloat32));
+  if (a.T == 0) return {ids, w};
+  a.x = x.data_ptr();
+  a.router = router.data_ptr();
+  a.ids = ids.data_ptr<int32_t>();
+  a.w = w.data_ptr<float>();
+  CHECK_HIP(lds_moe_route(a, cur_stream()));
+  return {ids, w};
+}
+
+// Byte offsets of the scratch arrays of moe_ffn, each 16-byte aligned, and
+// the total: act, y2, tiles, n_tiles, perm (MoeFfnArgs).
+struct MoeScratch { int64_t act, y2, tiles, n_tiles, perm, total; };
+
+MoeScratch moe_scratch_layout(int64_t T, int64_t k, int64_t E, int64_t H,
+                              int64_t I) {
+  const int64_t P = T * k;
+  const int mb = moe_mb(P, (int)E);
+  const int64_t n_tiles = moe_tile_bound(P, (int)E, mb);
+  const int64_t rows = n_tiles * 16 * mb;
+  auto up16 = [](int64_t b) { return (b + 15) / 16 * 16; };
+  MoeScratch s{};
+  s.act = 0;
+  s.y2 = s.act + up16(rows * I * 2);
+  s.tiles = s.y2 + up16(P * H * 4);
+  s.n_tiles = s.tiles + up16(n_tiles * 3 * 4);
+  s.perm = s.n_tiles + 16;
+  s.total = s.perm + up16(rows * 4);
+  return s;
+}
+
+int64_t moe_scratch_bytes(int64_t T, int64_t k, int64_t E, int64_t H,
+                          int64_t I) {
+  check_int(T, 0, INT_MAX / MOE_MAX_TOPK, "T");
+  check_int(k, 1, MOE_MAX_TOPK, "k");
+  check_int(E, 1, MOE_MAX_EXPERTS, "E");
+  check_int(H, 32, INT_MAX, "H");
+  check_int(I, 16, INT_MAX, "I");
+  return moe_scratch_layout(T, k, E, H, I).total;
+}
+
+// y [T, H] = the routed expert FFN of x (MoeFfnArgs). scratch: uint8, at
+// least moe_scratch_bytes long, or none to allocate it here. The entries of
+// ids are device data and are not checked (the kernels clamp them).
+torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor w13, torch::Tensor w2,
+                      torch::Tensor ids, torch::Tensor w,
+                      c10::optional<torch::Tensor> scratch) {
+  MoeFfnArgs a{};
+  a.T = check_moe_x(x);
+  a.H = (int)x.size(1);
+  check_tensor(w13, "w13", x, "x", at::kBFloat16, {ANY, ANY, x.size(1)});
+  a.E = check_int(w13.size(0), 1, MOE_MAX_EXPERTS, "w13.size(0)");
+  TORCH_CHECK(w13.size(1) % 32 == 0 && w13.size(1) >= 32, "w13.size(1) = 2 I "
+              "must be a positive multiple of 32, got ", w13.size(1));
+  a.I = check_int(w13.size(1) / 2, 16, INT_MAX, "w13.size(1) / 2");
+  check_tensor(w2, "w2", x, "x", at::kBFloat16, {a.E, a.H, a.I});
+  check_tensor(ids, "ids", x, "x", at::kInt, {a.T, ANY});
+  a.k = check_int(ids.size(1), 1, std::min<int64_t>(MOE_MAX_TOPK, a.E),
+                  "ids.size(1)");
+  check_tensor(w, "w", x, "x", at::kFloat, {a.T, a.k});
+  check_aligned16(w13, "w13");
+  check_aligned16(w2, "w2");
+  check_int((int64_t)a.E * 2 * a.I, 1, INT_MAX, "rows of w13");
+  const int64_t P = (int64_t)a.T * a.k;
+  a.mb = moe_mb(P, a.E);
+  check_int(moe_tile_bound(P, a.E, a.mb), 0, GRID_YZ_MAX, "work-list tiles");
+  check_int((a.H + 31) / 32, 1, INT_MAX, "column blocks");
+  const MoeScratch s = moe_scratch_layout(a.T, a.k, a.E, a.H, a.I);
+  if (scratch.has_value()) {
+    check_tensor(*scratch, "scratch", x, "x", at::kByte, {ANY});
+    TORCH_CHECK(scratch->size(0) >= s.total, "scratch must hold ", s.total,
+                " bytes, got ", scratch->size(0));
+    check_aligned16(*scratch, "scratch");
+  }
+  auto y = torch::empty({a.T, a.H}, x.options());
+  if (a.T == 0) return y;
+  torch::Tensor buf = scratch.has_value()
+      ? *scratch : torch::empty({s.total}, x.options().dtype(torch::kByte));
+  uint8_t* base = buf.data_ptr<uint8_t>();
+  a.x = x.data_ptr();
+  a.w13 = w13.data_ptr();
+  a.w2 = w2.data_ptr();
+  a.ids = ids.data_ptr<int32_t>();
+  a.w = w.data_ptr<float>();
+  a.y = y.data_ptr();
+  a.act = base + s.act;
+  a.y2 = (float*)(base + s.y2);
+  a.tiles = (int32_t*)(base + s.tiles);
+  a.n_tiles = (int32_t*)(base + s.n_tiles);
+  a.perm = (int32_t*)(base + s.perm);
+  CHECK_HIP(lds_moe_ffn(a, cur_stream()));
+  return y;
+}
+
 // ---- sampler ----
 
 // One per-row parameter vector of sample(): [B], on the logits' device.
@@ -1017,6 +1138,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequant_mxfp4_weight", &dequant_mxfp4_weight,
         "expand an MXFP4 weight into out [in, out] bf16",
         py::arg("wq"), py::arg("scale"), py::arg("out"));
+  m.def("moe_route", &moe_route,
+        "top-k of softmax(x [T, H] · router [E, H]^T) -> (ids [T, k] int32, "
+        "w [T, k] fp32)",
+        py::arg("x"), py::arg("router"), py::arg("k"), py::arg("renorm"));
+  m.def("moe_scratch_bytes", &moe_scratch_bytes,
+        "bytes of scratch moe_ffn needs",
+        py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));
+  m.def("moe_ffn", &moe_ffn,
+        "routed expert FFN: x [T, H], w13 [E, 2 I, H], w2 [E, H, I], ids and "
+        "w [T, k] -> y [T, H] bf16",
+        py::arg("x"), py::arg("w13"), py::arg("w2"), py::arg("ids"),
+        py::arg("w"), py::arg("scratch") = py::none());
   m.def("sample", &sample,
         "fused temperature/top-k/top-p/seeded sampler with logprobs -> "
         "(tokens, logprobs, n_kept, threshold)",

@@ -432,6 +432,9 @@ class EngineWorker:
         max_lora_rank rounded up to a multiple of 16 (DEVELOPMENT.md "LoRA
         adapters"); with max_loras=0 nothing is allocated and no request may
         name an adapter."""
+        if config.num_experts and max_loras > 0:
+            raise ValueError("LoRA adapters are not supported for an MoE "
+                             "model (max_loras must be 0)")
         self.cfg = config
         self.device = torch.device(device)
         self._is_cuda_dev = lambda: self.device.type == "cuda"

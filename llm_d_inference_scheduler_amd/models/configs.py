@@ -22,6 +22,32 @@ class ModelConfig:
     vision_hidden: int = 0
     vision_layers: int = 0
     vision_patches: int = 0
+    # mixture of experts (DEVELOPMENT.md "Mixture of experts"): num_experts
+    # == 0 is a dense FFN of intermediate_size. Otherwise every layer routes
+    # each token to experts_per_token of num_experts SwiGLU experts of
+    # moe_intermediate_size; norm_topk_prob: the softmax over all experts is
+    # renormalised over the chosen ones (False keeps the raw softmax values)
+    num_experts: int = 0
+    experts_per_token: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = True
+
+    def __post_init__(self):
+        if self.num_experts == 0:
+            return
+        if not 2 <= self.num_experts <= 256:
+            raise ValueError(f"num_experts must be 0 or in [2, 256], got "
+                             f"{self.num_experts}")
+        if not 1 <= self.experts_per_token <= min(8, self.num_experts):
+            raise ValueError(f"experts_per_token must be in [1, min(8, "
+                             f"num_experts)], got {self.experts_per_token}")
+        if self.hidden_size % 32:
+            raise ValueError(f"an MoE model needs hidden_size % 32 == 0, got "
+                             f"{self.hidden_size}")
+        if self.moe_intermediate_size < 16 or self.moe_intermediate_size % 16:
+            raise ValueError(f"moe_intermediate_size must be a positive "
+                             f"multiple of 16, got "
+                             f"{self.moe_intermediate_size}")
 
     @property
     def q_size(self) -> int:
@@ -73,3 +99,18 @@ TINY_LLAVA = ModelConfig(
     intermediate_size=512, num_layers=2, num_heads=8, num_kv_heads=4,
     head_dim=32, rope_theta=10000.0, max_position=512,
     vision_hidden=64, vision_layers=2, vision_patches=8)
+
+# Qwen3-30B-A3B: 128 experts, 8 a token, 768 wide; intermediate_size is the
+# dense FFN width of the family and is not used by an MoE layer
+QWEN3_30B_A3B = ModelConfig(
+    name="qwen3-30b-a3b", vocab_size=151936, hidden_size=2048,
+    intermediate_size=6144, num_layers=48, num_heads=32, num_kv_heads=4,
+    head_dim=128, rope_theta=1000000.0, rms_eps=1e-6, qk_norm=True,
+    max_position=8192, num_experts=128, experts_per_token=8,
+    moe_intermediate_size=768)
+
+TINY_MOE = ModelConfig(
+    name="tiny-moe", vocab_size=1024, hidden_size=256,
+    intermediate_size=512, num_layers=2, num_heads=8, num_kv_heads=4,
+    head_dim=32, rope_theta=10000.0, max_position=512,
+    num_experts=8, experts_per_token=2, moe_intermediate_size=128)

@@ -11,6 +11,7 @@ multi-backend dispatch is used anywhere).
 The reference router never runs a model — its pods do (vLLM). This runner
 is the per-GPU worker engine's model, SURVEY.md §2.12 "worker shim".
 """
+import dataclasses
 import math
 import os
 from dataclasses import dataclass
@@ -102,6 +103,9 @@ class LlamaRunner:
         # compare the two paths)
         self._fused_qkv = True
         c = config
+        if c.num_experts and self.device.type == "cuda" and \
+                dtype != torch.bfloat16:
+            raise ValueError("an MoE model on the GPU needs a bf16 runner")
         if self.device.type == "cuda":
             _load_tuned_gemms()
             # init directly on the GPU (16 GB of weights for Llama-3-8B —
@@ -138,8 +142,15 @@ class LlamaRunner:
                     "k_norm": torch.ones(c.head_dim, dtype=dtype,
                                          device=device)}
                    if c.qk_norm else {}),
-                "wgate_up": w(c.hidden_size, 2 * c.intermediate_size),
-                "wdown": w(c.intermediate_size, c.hidden_size, std=out_std),
+                **({"router": w(c.num_experts, c.hidden_size),
+                    "w13": w(c.num_experts, 2 * c.moe_intermediate_size,
+                             c.hidden_size),
+                    "w2": w(c.num_experts, c.hidden_size,
+                            c.moe_intermediate_size, std=out_std)}
+                   if c.num_experts else
+                   {"wgate_up": w(c.hidden_size, 2 * c.intermediate_size),
+                    "wdown": w(c.intermediate_size, c.hidden_size,
+                               std=out_std)}),
             })
         self.final_norm = torch.ones(c.hidden_size, dtype=dtype, device=device)
         self.lm_head = self.embed if c.tie_embeddings else \
@@ -155,6 +166,8 @@ class LlamaRunner:
         self._fp8_kernel_max_t = 128
         self._mxfp4_kernel_max_t = 128
         self._fp8_scratch: Dict[int, torch.Tensor] = {}
+        # ops.moe_ffn scratch, one per stream, sized by the largest T seen
+        self._moe_scratch: Dict[int, torch.Tensor] = {}
 
     def weight_bytes(self) -> int:
         tensors = [self.embed, self.lm_head, self.final_norm]
@@ -178,6 +191,9 @@ class LlamaRunner:
             return
         if weight_dtype not in ("fp8", "mxfp4"):
             raise ValueError(f"unknown weight_dtype {weight_dtype!r}")
+        if self.cfg.num_experts:
+            raise ValueError(f"{weight_dtype} weights are not supported for "
+                             "an MoE model: the experts are bf16")
         if self.weight_dtype == weight_dtype:
             return
         if self.weight_dtype != "bf16":
@@ -205,6 +221,56 @@ class LlamaRunner:
             return (w[0].float() * w[1][:, None]).t()
         return [{k: dense(w) if k in LORA_TARGETS else w
                  for k, w in layer.items()} for layer in self.layers]
+
+    # ---- mixture of experts (DEVELOPMENT.md "Mixture of experts") ----
+    def upcycle_to_moe(self, num_experts: int, experts_per_token: int,
+                       seed: int = 0) -> None:
+        """Sparse upcycling of a dense runner, in place: every layer's w13
+        and w2 become num_experts copies of its transposed wgate_up and
+        wdown, the router is drawn at random, and self.cfg becomes the MoE
+        config with norm_topk_prob=True. With identical experts and
+        renormalised weights the layer computes the dense FFN in exact
+        arithmetic, whichever experts a token is routed to. Dense weights in
+        the runner's dtype only."""
+        if self.cfg.num_experts:
+            raise ValueError("the runner is already an MoE model")
+        if self.weight_dtype != "bf16":
+            raise ValueError(f"cannot upcycle {self.weight_dtype} weights")
+        cfg = dataclasses.replace(
+            self.cfg, num_experts=num_experts,
+            experts_per_token=experts_per_token,
+            moe_intermediate_size=self.cfg.intermediate_size,
+            norm_topk_prob=True)
+        if self.device.type == "cuda" and self.dtype != torch.bfloat16:
+            raise ValueError("an MoE model on the GPU needs a bf16 runner")
+        gen = torch.Generator(device="cpu").manual_seed(seed)
+        for layer in self.layers:
+            router = torch.empty(num_experts, cfg.hidden_size)
+            router.normal_(0.0, 0.02, generator=gen)
+            layer["router"] = router.to(self.dtype).to(self.device)
+            w13 = layer.pop("wgate_up").t().contiguous()
+            w2 = layer.pop("wdown").t().contiguous()
+            layer["w13"] = w13.unsqueeze(0).repeat(num_experts, 1, 1)
+            layer["w2"] = w2.unsqueeze(0).repeat(num_experts, 1, 1)
+        self.cfg = cfg
+
+    def _moe(self, x: torch.Tensor, layer) -> torch.Tensor:
+        """The routed FFN of one layer. Nothing on this path waits for the
+        device: routing and the work list stay there."""
+        c = self.cfg
+        ids, w = ops.moe_route(x, layer["router"], c.experts_per_token,
+                               c.norm_topk_prob)
+        if not x.is_cuda:
+            return ops.moe_ffn(x, layer["w13"], layer["w2"], ids, w)
+        key = torch.cuda.current_stream(x.device).cuda_stream
+        need = ops.moe_scratch_bytes(x.shape[0], c.experts_per_token,
+                                     c.num_experts, c.hidden_size,
+                                     c.moe_intermediate_size)
+        buf = self._moe_scratch.get(key)
+        if buf is None or buf.numel() < need:
+            buf = self._moe_scratch[key] = torch.empty(
+                need, dtype=torch.uint8, device=x.device)
+        return ops.moe_ffn(x, layer["w13"], layer["w2"], ids, w, buf)
 
     def _linear(self, x: torch.Tensor, w) -> torch.Tensor:
         """x @ w for a projection of self.layers: dense, an fp8 pair or an
@@ -254,6 +320,9 @@ class LlamaRunner:
         lora = batch.lora
         if lora is not None and lora_weights is None:
             raise ValueError("batch.lora needs lora_weights")
+        if lora is not None and c.num_experts:
+            raise ValueError("LoRA adapters are not supported for an MoE "
+                             "model")
 
         def lora_add(y, x, li, target):
             A, B = lora_weights[li][target]
@@ -330,6 +399,9 @@ class LlamaRunner:
                 lora_add(o, attn, li, "wo")
             normed2 = ops.rmsnorm(o, layer["post_norm"], c.rms_eps,
                                   residual=residual)
+            if c.num_experts:
+                hidden = self._moe(normed2, layer)
+                continue
             gate_up = self._linear(normed2, layer["wgate_up"])
             if lora is not None:
                 lora_add(gate_up, normed2, li, "wgate_up")

@@ -276,6 +276,38 @@ def dequant_mxfp4_weight(wq: torch.Tensor, scale: torch.Tensor,
     return ref.dequant_mxfp4_weight(wq, scale, out)
 
 
+def moe_route(x: torch.Tensor, router: torch.Tensor, k: int,
+              renorm: bool = True):
+    """Expert routing on the device (DEVELOPMENT.md "Mixture of experts"):
+    x [T, H], router [E, H] -> (ids [T, k] int32, w [T, k] fp32), the k
+    largest of softmax(x · routerᵀ) per token, value descending, ties to the
+    lower index; with renorm divided by their sum. H % 32 == 0, E <= 256,
+    k <= min(8, E)."""
+    if _use_hip(x):
+        ids, w = _ext.moe_route(x, router, k, renorm)
+        return ids, w
+    return ref.moe_route(x, router, k, renorm)
+
+
+def moe_scratch_bytes(T: int, k: int, E: int, H: int, I: int) -> int:
+    """Bytes of the scratch ops.moe_ffn takes for T tokens."""
+    return hip_ops().moe_scratch_bytes(T, k, E, H, I)
+
+
+def moe_ffn(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
+            ids: torch.Tensor, w: torch.Tensor,
+            scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The routed expert FFN: x [T, H], w13 [E, 2 I, H] (gate rows, then up
+    rows), w2 [E, H, I], ids int32 / w fp32 [T, k] -> y [T, H], y[t] = sum_j
+    w[t, j] * (bf16(silu(x[t] Wg_e) * (x[t] Wu_e)) W2_e) with e = ids[t, j],
+    fp32 sums, j in slot order. I % 16 == 0. scratch (GPU only): a uint8
+    tensor of at least moe_scratch_bytes, or None to allocate per call. No
+    host synchronisation: the work list is built on the device."""
+    if _use_hip(x):
+        return _ext.moe_ffn(x, w13, w2, ids, w, scratch)
+    return ref.moe_ffn(x, w13, w2, ids, w)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

@@ -800,6 +800,44 @@ def linear_mxfp4(x: torch.Tensor, wq: torch.Tensor,
     return (x.float() @ _mxfp4_dense_f32(wq, scale).t()).to(x.dtype)
 
 
+# ---- mixture of experts (DEVELOPMENT.md "Mixture of experts") --------------
+
+def moe_route(x: torch.Tensor, router: torch.Tensor, k: int, renorm: bool):
+    """x [T, H], router [E, H] -> (ids [T, k] int32, w [T, k] fp32): fp32
+    logits, softmax over all E, the k largest (value descending, ties to the
+    lower index), divided by their sum with renorm."""
+    p = torch.softmax(x.float() @ router.float().t(), dim=-1)
+    order = torch.sort(p, dim=-1, descending=True, stable=True).indices[:, :k]
+    w = torch.gather(p, 1, order)
+    if renorm:
+        w = w / w.sum(dim=-1, keepdim=True)
+    return order.to(torch.int32), w
+
+
+def moe_ffn(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
+            ids: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """x [T, H], w13 [E, 2 I, H] (gate rows, then up rows), w2 [E, H, I],
+    ids / w [T, k] -> y [T, H] in x's dtype: y[t] = sum_j w[t, j] *
+    (act(x[t], e) · w2[e]ᵀ) with e = ids[t, j], act = silu(x · Wgᵀ) *
+    (x · Wuᵀ) rounded once to x's dtype, fp32 sums, j in slot order, one final
+    rounding."""
+    T, H = x.shape
+    I, k = w13.shape[1] // 2, ids.shape[1]
+    xf = x.float()
+    y2 = torch.zeros(T, k, H, dtype=torch.float32, device=x.device)
+    for e in range(w13.shape[0]):
+        t, j = (ids == e).nonzero(as_tuple=True)
+        if t.numel() == 0:
+            continue
+        g, u = (xf[t] @ w13[e].float().t()).split(I, dim=-1)
+        act = (g * torch.sigmoid(g) * u).to(x.dtype).float()
+        y2[t, j] = (act @ w2[e].float().t()) * w[t, j].float()[:, None]
+    y = y2[:, 0]
+    for j in range(1, k):
+        y = y + y2[:, j]
+    return y.to(x.dtype)
+
+
 _PREFIX_MODEL = PrefixModel()
 hash_prompts = _PREFIX_MODEL.hash_prompts
 table_update = _PREFIX_MODEL.table_update

@@ -26,7 +26,7 @@ def parse_args(argv=None):
                         "the reference's default grpcPort is 9002)")
     p.add_argument("--model", default="llama-3-8b",
                    choices=["llama-3-8b", "qwen3-32b", "llava-1.5-7b",
-                            "tiny-llama"])
+                            "tiny-llama", "qwen3-30b-a3b", "tiny-moe"])
     p.add_argument("--topology", default="mono",
                    help='"mono", "pd-combined", "pd:NpMd", "epd:1eNpMd"')
     p.add_argument("--config-file", default="",
@@ -80,11 +80,13 @@ def build_node(args):
     import torch
 
     from ..models.configs import (LLAMA_3_8B, LLAVA_1_5_7B_TEXT,
-                                  QWEN3_32B, TINY_LLAMA)
+                                  QWEN3_30B_A3B, QWEN3_32B, TINY_LLAMA,
+                                  TINY_MOE)
     from ..node import NodeConfig, NodeRunner
     model = {"llama-3-8b": LLAMA_3_8B, "qwen3-32b": QWEN3_32B,
              "llava-1.5-7b": LLAVA_1_5_7B_TEXT,
-             "tiny-llama": TINY_LLAMA}[args.model]
+             "tiny-llama": TINY_LLAMA, "qwen3-30b-a3b": QWEN3_30B_A3B,
+             "tiny-moe": TINY_MOE}[args.model]
     use_gpu = torch.cuda.is_available() if args.device is None else \
         str(args.device).startswith("cuda")
     device = args.device or ("cuda:0" if use_gpu else "cpu")

@@ -42,6 +42,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/lora.hip",
         "csrc/hip/linear_fp8.hip",
         "csrc/hip/linear_mxfp4.hip",
+        "csrc/hip/moe.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],

@@ -1,0 +1,161 @@
+"""Microbench of the MoE layer (ops.moe_route + ops.moe_ffn) at
+Qwen3-30B-A3B shapes (results: profiles/moe.md).
+
+    python tools/moe_bench.py [--rounds 7] [--copies 8]
+
+One layer: H 2048, 128 experts of I 768, 8 a token, for T in {1, 16, 64, 256,
+1024, 4096}. Arms, timed in one process in interleaved rounds (arm order
+rotates each round) with device events around a window of back-to-back calls
+(enough for 10 ms of device time), on random data:
+  kernel   ops.moe_route, then ops.moe_ffn with a resident scratch, as the
+           runner calls them: five launches and no host synchronisation
+  torch    the same math composed from torch ops: matmul, softmax, topk, and
+           per expert nonzero + index_select + two matmuls + index_add. The
+           nonzero makes the host wait once per expert; that wait is part of
+           what the composition costs.
+A decode step streams every layer's weights, so a layer's experts are cold
+when its FFN starts. Each arm therefore walks round-robin over --copies
+copies of the layer (router, w13, w2) and as many different x: a call never
+finds its experts where the call before left them, as long as copies times
+the touched bytes exceed the 256 MB Infinity Cache (at T = 1 that needs 4).
+Before a T is timed, both arms are compared with float64 under the bound of
+tests/moe_cases.py.
+Reported per arm: the median per-call time over the rounds and the largest
+minus the smallest round, in us; `floor` is the bytes of the router and of
+the experts the calls actually touch (mean over the copies) over 8 TB/s;
+`experts` is that mean count.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import moe_cases  # noqa: E402
+from llm_d_inference_scheduler_amd import ops  # noqa: E402
+from llm_d_inference_scheduler_amd.models.configs import (  # noqa: E402
+    QWEN3_30B_A3B)
+
+DEV = "cuda"
+TS = (1, 16, 64, 256, 1024, 4096)
+WINDOW_US = 10000.0
+HBM_BYTES_PER_US = 8e6
+
+
+def time_arm(fn, iters):
+    start = torch.cuda.Event(enable_timing=True)
+    end = torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) * 1e3 / iters          # us per call
+
+
+def bench(fns, rounds):
+    names = list(fns)
+    for fn in fns.values():                                # warm-up
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    iters = {n: max(5, int(WINDOW_US / time_arm(fns[n], 5)) + 1)
+             for n in names}
+    times = {n: [] for n in names}
+    for r in range(rounds):
+        for n in names[r % len(names):] + names[:r % len(names)]:
+            times[n].append(time_arm(fns[n], iters[n]))
+    res = {n: round(statistics.median(ts), 2) for n, ts in times.items()}
+    res.update({n + "_spread": round(max(ts) - min(ts), 2)
+                for n, ts in times.items()})
+    return res
+
+
+def rotating(fn, n):
+    """fn(i) over i = 0 .. n - 1, round-robin, one step a call."""
+    state = [0]
+
+    def call():
+        state[0] = (state[0] + 1) % n
+        return fn(state[0])
+    return call
+
+
+def torch_route(x, router, k):
+    p = torch.softmax(x.float() @ router.float().t(), dim=-1)
+    w, ids = torch.topk(p, k, dim=-1)
+    return ids, w / w.sum(dim=-1, keepdim=True)
+
+
+def torch_moe(x, router, w13, w2, k):
+    """The layer from torch ops, bf16 GEMMs, per expert over its rows."""
+    ids, w = torch_route(x, router, k)
+    I = w2.shape[2]
+    y = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    for e in range(w13.shape[0]):
+        t, j = (ids == e).nonzero(as_tuple=True)
+        if t.numel() == 0:
+            continue
+        g, u = (x.index_select(0, t) @ w13[e].t()).split(I, dim=-1)
+        act = torch.nn.functional.silu(g) * u
+        y.index_add_(0, t, (act @ w2[e].t()).float() * w[t, j][:, None])
+    return y.to(x.dtype)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--copies", type=int, default=8)
+    args = ap.parse_args()
+    ops.hip_ops()
+    c = QWEN3_30B_A3B
+    H, I, E, k = (c.hidden_size, c.moe_intermediate_size, c.num_experts,
+                  c.experts_per_token)
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    randn = lambda *s: torch.randn(*s, generator=gen, device=DEV)
+    n = args.copies
+    routers = [randn(E, H).mul_(0.02).bfloat16() for _ in range(n)]
+    w13s = [randn(E, 2 * I, H).mul_(0.02).bfloat16() for _ in range(n)]
+    w2s = [randn(E, H, I).mul_(0.02).bfloat16() for _ in range(n)]
+    expert_bytes = 3 * I * H * 2
+    for T in TS:
+        xs = [randn(T, H).bfloat16() for _ in range(n)]
+        scratch = torch.empty(ops.moe_scratch_bytes(T, k, E, H, I),
+                              dtype=torch.uint8, device=DEV)
+
+        def kernel(i):
+            ids, w = ops.moe_route(xs[i], routers[i], k, True)
+            return ops.moe_ffn(xs[i], w13s[i], w2s[i], ids, w, scratch)
+
+        def composed(i):
+            return torch_moe(xs[i], routers[i], w13s[i], w2s[i], k)
+
+        ids, w = ops.moe_route(xs[0], routers[0], k, True)
+        moe_cases.check_route(ids, w, xs[0], routers[0], k, True)
+        for what, y in (("kernel", kernel(0)), ("torch", composed(0))):
+            excess = moe_cases.ffn_excess(y, xs[0], w13s[0], w2s[0], ids, w)
+            # the composition rounds g, u and the expert output to bf16 as
+            # well: three more half-ulps of |y| than the bound allows for
+            if excess > 0 and what == "kernel":
+                raise SystemExit(f"T={T} {what}: excess {excess:.3e}")
+            print(f"# T={T} {what} excess {excess:.3e}", flush=True)
+        touched = statistics.mean(
+            int(torch_route(xs[i], routers[i], k)[0].unique().numel())
+            for i in range(n))
+        fns = {"kernel": rotating(kernel, n), "torch": rotating(composed, n)}
+        print(json.dumps(dict(
+            T=T, H=H, I=I, E=E, k=k, copies=n, experts=round(touched, 1),
+            floor=round((touched * expert_bytes + E * H * 2)
+                        / HBM_BYTES_PER_US, 2),
+            **bench(fns, args.rounds))), flush=True)
+        del xs, scratch
+
+
+if __name__ == "__main__":
+    main()
