@@ -293,6 +293,39 @@ struct MoeFfnArgs {
 
 hipError_t lds_moe_ffn(const MoeFfnArgs& a, hipStream_t stream);
 
+// Row blocks of a work-list tile on MXFP4 experts: a ring stage of the 4-bit
+// kernels holds 16 registers a row block, and MB = 4 leaves no room for a
+// ring, so taller segments walk more tiles of 32 rows.
+constexpr int MOE_MXFP4_MAX_MB = 2;
+inline int moe_mxfp4_mb(int64_t P, int E) {
+  const int mb = moe_mb(P, E);
+  return mb < MOE_MXFP4_MAX_MB ? mb : MOE_MXFP4_MAX_MB;
+}
+
+// moe_ffn on MXFP4 experts: y is what MoeFfnArgs computes on the exactly
+// dequantised experts e2m1(code) * 2^(scale - 127), every one of which is a
+// bf16. Codes: two a byte, k = 2j in the low nibble; one e8m0 scale per 32 k.
+struct MoeFfnMxfp4Args {
+  const void* x;        // [T, H] bf16, H % 32 == 0, 16-byte aligned
+  const void* w13q;     // [E, 2 I, H / 2] uint8, 16-byte aligned
+  const void* w13s;     // [E, 2 I, H / 32] uint8
+  const void* w2q;      // [E, H, I / 2] uint8, I % 32 == 0, 16-byte aligned
+  const void* w2s;      // [E, H, I / 32] uint8
+  const int32_t* ids;   // [T, k]
+  const float* w;       // [T, k]
+  void* y;              // [T, H] bf16
+  // scratch as in MoeFfnArgs, with mb below
+  void* act;
+  float* y2;
+  int32_t* tiles;
+  int32_t* n_tiles;
+  int32_t* perm;
+  int T, H, I, E, k;
+  int mb;               // moe_mxfp4_mb(T * k, E)
+};
+
+hipError_t lds_moe_ffn_mxfp4(const MoeFfnMxfp4Args& a, hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

@@ -64,6 +64,7 @@
 // other rows of the launch.
 #include "hip_common.h"
 #include "launchers.h"
+#include "mxfp4_convert.h"
 
 // Built without packed fp32 arithmetic, for the reason given in
 // linear_fp8.hip: the fp32 work here is three adds per output element.
@@ -76,31 +77,11 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 constexpr int MX_THREADS = 256;
 constexpr int MX_WAVES = MX_THREADS / WAVE;
 constexpr int MX_ROWS = 32;    // rows of a grid.y tile
 constexpr int MX_GROUP = 32;   // k that share one e8m0 scale
-
-// e8m0 byte -> 2^(byte - 127): the byte is the exponent field
-__device__ __forceinline__ float e8m0_to_f32(uint32_t b) {
-  union { uint32_t i; float f; } c;
-  c.i = b << 23;
-  return c.f;
-}
-
-// 8 e2m1 codes (one dword, k ascending from the low nibble of byte 0) times
-// sc -> the 8 bf16 of one MFMA operand. The convert puts the low nibble of
-// the selected byte in the low half of its result.
-__device__ __forceinline__ short8 fp4x8_to_bf16(uint32_t v, float sc) {
-  union { bf16x2 h[4]; short8 s; } u;
-  u.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 0);
-  u.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 1);
-  u.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 2);
-  u.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 3);
-  return u.s;
-}
 
 // One ring stage of this lane: per column block one MX group (16 bytes of
 // codes, one scale byte), per row block the 32 x of the same k.

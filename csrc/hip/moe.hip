@@ -37,6 +37,33 @@
 // grids are launched at the host-known bound moe_tile_bound; a workgroup
 // whose tile index is >= n_tiles returns at once.
 //
+// MXFP4 experts (moe_ffn_mxfp4): w13q [E, 2 I, H / 2] and w2q [E, H, I / 2]
+// uint8, two e2m1 codes a byte with k = 2j in the low nibble, and w13s
+// [E, 2 I, H / 32], w2s [E, H, I / 32] uint8, one e8m0 exponent per 32 k: the
+// pair of ops.ref.quantize_weight_mxfp4 per expert. x, act, y2 and y are as
+// above, and so are the work list, the tiles, the epilogues and the combine.
+//   moe_gate_up_mxfp4_kernel<MB>, moe_down_mxfp4_kernel<MB>   the same grids.
+//     What changes is the K loop (mx_gemm_core): its unit is that of
+//     linear_mxfp4_kernel. A stage is a 128-wide K block; lane group
+//     g = lane >> 4 owns MX group g of it. One 16-byte load is the 32 codes
+//     of weight row lane & 15 in that group, one byte load is their scale,
+//     and four 16-byte loads are the lane's x row at the same 32 k. Dword q
+//     of the codes goes through four v_cvt_scalef32_pk_bf16_fp4 with the
+//     scale as operand and is the B operand of MFMA q; the MFMA sums over its
+//     four lane groups whatever k each brings, so a lane only multiplies k of
+//     its own group and the scale costs no instruction. The waves take the K
+//     blocks round-robin, a register ring keeps the next DEPTH blocks in
+//     flight, and the accumulators meet in LDS as above.
+//   K tail. K % 32 == 0 is all that is asked (gpt-oss: 2880 = 22 * 128 + 64).
+//     The last K block may hold one to three groups: a lane group past K
+//     issues no load and feeds zeros on both operands.
+//   Tile height. A stage is 5 NW + 16 MB registers a lane: 36 and 52 for
+//     gate-up (NW 4) at MB 1 and 2, 26 and 42 for down. At MB 4 a stage would
+//     be 84: no ring fits next to 64 accumulators. So the MXFP4 work list is
+//     built with MB <= 2 (moe_mxfp4_mb): a taller segment walks more tiles,
+//     and its weights come from L2 after the first. A pair's bits do not
+//     depend on that choice either.
+//
 // Determinism: no atomic touches floating-point data. The bits of a pair
 // depend on its x row, its expert and its routing weight only: MFMA rows and
 // columns never mix, the K step -> wave assignment depends on K alone and
@@ -44,6 +71,7 @@
 // the pair's position in its segment or on the other rows of the launch.
 #include "hip_common.h"
 #include "launchers.h"
+#include "mxfp4_convert.h"
 
 // Built without packed fp32 arithmetic, as linear_fp8.hip is and for the
 // reason given there.
@@ -370,6 +398,46 @@ __device__ __forceinline__ f32x4 red_sum(
   return s;
 }
 
+// The epilogues, shared by the bf16 and the MXFP4 kernels. Gate-up: act =
+// bf16(silu(gate) * up) for the tile's live rows, by sorted position.
+template <int MB>
+__device__ __forceinline__ void gate_up_epilogue(
+    const float (&red)[MOE_WAVES][MB][2 * MOE_NB][4][WAVE],
+    short* __restrict__ act, int start, int count, int n0, int I) {
+  constexpr int NW = 2 * MOE_NB;
+  for (int i = threadIdx.x; i < count * (MOE_BN / 4); i += MOE_THREADS) {
+    const int m = i / (MOE_BN / 4), c = (i % (MOE_BN / 4)) * 4;
+    const int n = n0 + c;
+    if (n >= I) continue;  // I % 16 == 0: four columns are in or out
+    const f32x4 g = red_sum<MB, NW>(red, m, c >> 4, c & 15);
+    const f32x4 u = red_sum<MB, NW>(red, m, MOE_NB + (c >> 4), c & 15);
+    short4v o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      o[e] = f32_to_bf16(g[e] / (1.f + expf(-g[e])) * u[e]);
+    *(short4v*)(act + (int64_t)(start + m) * I + n) = o;
+  }
+}
+
+// Down: y2[pair] = the pair's routing weight times its row, fp32.
+template <int MB>
+__device__ __forceinline__ void down_epilogue(
+    const float (&red)[MOE_WAVES][MB][MOE_NB][4][WAVE],
+    const int32_t* __restrict__ perm, const float* __restrict__ w,
+    float* __restrict__ y2, int start, int count, int n0, int H) {
+  for (int i = threadIdx.x; i < count * (MOE_BN / 4); i += MOE_THREADS) {
+    const int m = i / (MOE_BN / 4), c = (i % (MOE_BN / 4)) * 4;
+    const int n = n0 + c;
+    if (n >= H) continue;  // H % 32 == 0
+    const int pair = perm[start + m];
+    const float wt = w[pair];
+    f32x4 s = red_sum<MB, MOE_NB>(red, m, c >> 4, c & 15);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[e] *= wt;
+    *(f32x4*)(y2 + (int64_t)pair * H + n) = s;
+  }
+}
+
 // ring depth by registers: a stage holds NW + MB 16-byte loads a lane
 template <int MB>
 constexpr int gate_up_depth() { return MB == 4 ? 3 : 4; }
@@ -410,18 +478,7 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_gate_up_kernel(
   }
   gemm_core<MB, NW, gate_up_depth<MB>(), false>(red, wp, xp, H, H - kq);
 
-  for (int i = threadIdx.x; i < count * (MOE_BN / 4); i += MOE_THREADS) {
-    const int m = i / (MOE_BN / 4), c = (i % (MOE_BN / 4)) * 4;
-    const int n = n0 + c;
-    if (n >= I) continue;  // I % 16 == 0: four columns are in or out
-    const f32x4 g = red_sum<MB, NW>(red, m, c >> 4, c & 15);
-    const f32x4 u = red_sum<MB, NW>(red, m, MOE_NB + (c >> 4), c & 15);
-    short4v o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      o[e] = f32_to_bf16(g[e] / (1.f + expf(-g[e])) * u[e]);
-    *(short4v*)(act + (int64_t)(start + m) * I + n) = o;
-  }
+  gate_up_epilogue<MB>(red, act, start, count, n0, I);
 }
 
 template <int MB>
@@ -454,17 +511,7 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_down_kernel(
   }
   gemm_core<MB, NW, down_depth<MB>(), true>(red, wp, xp, I, I - kq);
 
-  for (int i = threadIdx.x; i < count * (MOE_BN / 4); i += MOE_THREADS) {
-    const int m = i / (MOE_BN / 4), c = (i % (MOE_BN / 4)) * 4;
-    const int n = n0 + c;
-    if (n >= H) continue;  // H % 32 == 0
-    const int pair = perm[start + m];
-    const float wt = w[pair];
-    f32x4 s = red_sum<MB, NW>(red, m, c >> 4, c & 15);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[e] *= wt;
-    *(f32x4*)(y2 + (int64_t)pair * H + n) = s;
-  }
+  down_epilogue<MB>(red, perm, w, y2, start, count, n0, H);
 }
 
 // eight columns a thread: k reads of 32 bytes, one 16-byte write
@@ -495,6 +542,225 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_combine_kernel(
   *(short8*)(y + t * H + c) = o;
 }
 
+// ---- the two expert GEMMs on MXFP4 experts ---------------------------------
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+constexpr int MX_GROUP = 32;     // k that share one e8m0 scale
+constexpr int MX_KBLOCK = 128;   // k of one stage: a group a lane group
+
+// One ring stage of this lane: per weight row block one MX group (16 bytes
+// of codes, one scale byte), per x row block the 32 x of the same k.
+template <int MB, int NW>
+struct MxStage {
+  u32x4 w[NW];
+  uint32_t s[NW];
+  short8 x[MB][4];
+};
+
+// K block kb of this lane's group. groups_left = K / 32 - (lane >> 4): a
+// lane group whose k is past K issues no load and feeds zeros on both
+// operands (code 0 is +0 under any scale).
+template <int MB, int NW>
+__device__ __forceinline__ void mx_load_stage(
+    MxStage<MB, NW>& s, const unsigned char* const (&wp)[NW],
+    const unsigned char* const (&sp)[NW], const short* const (&xp)[MB],
+    int kb, int groups_left) {
+  const bool ok = kb * (MX_KBLOCK / MX_GROUP) < groups_left;
+  const u32x4 zw = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int n = 0; n < NW; ++n) {
+    s.w[n] = ok ? *(const u32x4*)(wp[n] + kb * (MX_KBLOCK / 2)) : zw;
+    s.s[n] = ok ? sp[n][kb * (MX_KBLOCK / MX_GROUP)] : 127u;
+  }
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      s.x[m][d] = load8_or_zero(xp[m] + kb * MX_KBLOCK + d * 8, ok);
+}
+
+// One turn of the ring, as ring_round: dword q of a stage's group is the B
+// operand of MFMA q, converted with the group's scale, against the lane's x
+// at the same eight k.
+template <int MB, int NW, int DEPTH, bool TAIL>
+__device__ __forceinline__ void mx_ring_round(
+    MxStage<MB, NW> (&ring)[DEPTH], f32x4 (&acc)[MB][NW],
+    const unsigned char* const (&wp)[NW],
+    const unsigned char* const (&sp)[NW], const short* const (&xp)[MB],
+    int wave, int groups_left, int i, int n_it) {
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) {
+    if (TAIL && i + d >= n_it) break;
+#pragma unroll
+    for (int n = 0; n < NW; ++n) {
+      const float sc = e8m0_to_f32(ring[d].s[n]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const short8 b = fp4x8_to_bf16(ring[d].w[n][q], sc);
+#pragma unroll
+        for (int m = 0; m < MB; ++m)
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              ring[d].x[m][q], b, acc[m][n], 0, 0, 0);
+      }
+    }
+    if (!TAIL || i + d + DEPTH < n_it)
+      mx_load_stage(ring[d], wp, sp, xp, wave + (i + d + DEPTH) * MOE_WAVES,
+                    groups_left);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// gemm_core for MXFP4 weight rows: this wave's 128-wide K blocks (wave,
+// wave + 4, ... below ceil(K / 128)), then all four waves' accumulators into
+// red. wp, sp and xp point at this lane's group of K block 0 of each row.
+// K % 32 == 0; the last block may hold one to three groups.
+template <int MB, int NW, int DEPTH>
+__device__ __forceinline__ void mx_gemm_core(
+    float (&red)[MOE_WAVES][MB][NW][4][WAVE],
+    const unsigned char* const (&wp)[NW],
+    const unsigned char* const (&sp)[NW], const short* const (&xp)[MB],
+    int K) {
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+  const int groups_left = K / MX_GROUP - (lane >> 4);
+  f32x4 acc[MB][NW];
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int n = 0; n < NW; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int n_kb = (K + MX_KBLOCK - 1) / MX_KBLOCK;
+  const int n_it = (n_kb - wave + MOE_WAVES - 1) / MOE_WAVES;  // may be 0
+  MxStage<MB, NW> ring[DEPTH];
+  int i = 0;
+  if (n_it >= 2 * DEPTH) {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) {
+      mx_load_stage(ring[d], wp, sp, xp, wave + d * MOE_WAVES, groups_left);
+      __builtin_amdgcn_sched_barrier(0);  // issue the stages in ring order
+    }
+    for (; i + 2 * DEPTH <= n_it; i += DEPTH)
+      mx_ring_round<MB, NW, DEPTH, false>(ring, acc, wp, sp, xp, wave,
+                                          groups_left, i, n_it);
+  } else {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d)
+      if (d < n_it)
+        mx_load_stage(ring[d], wp, sp, xp, wave + d * MOE_WAVES, groups_left);
+  }
+  for (; i < n_it; i += DEPTH)
+    mx_ring_round<MB, NW, DEPTH, true>(ring, acc, wp, sp, xp, wave,
+                                       groups_left, i, n_it);
+
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int n = 0; n < NW; ++n)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) red[wave][m][n][j][lane] = acc[m][n][j];
+  __syncthreads();
+}
+
+// ring depth by registers: a stage holds 5 NW + 16 MB a lane. Gate-up
+// (NW 4): 36 at MB 1, 52 at MB 2; down (NW 2): 26 and 42. MB 4 would be 84
+// and 74 a stage, no room for a ring: MOE_MXFP4_MAX_MB caps the tiles at 2.
+template <int MB>
+constexpr int mx_gate_up_depth() { return MB == 1 ? 4 : 3; }
+template <int MB>
+constexpr int mx_down_depth() { return 4; }
+
+// As moe_gate_up_kernel, on w13q [E, 2 I, H / 2] and w13s [E, 2 I, H / 32].
+// I % 32 == 0: every column block is whole.
+template <int MB>
+__global__ __launch_bounds__(MOE_THREADS) void moe_gate_up_mxfp4_kernel(
+    const short* __restrict__ x, const unsigned char* __restrict__ w13q,
+    const unsigned char* __restrict__ w13s, const int32_t* __restrict__ tiles,
+    const int32_t* __restrict__ n_tiles, const int32_t* __restrict__ perm,
+    short* __restrict__ act, int H, int I, int k) {
+  constexpr int NW = 2 * MOE_NB;   // gate blocks, then up blocks
+  __shared__ float red[MOE_WAVES][MB][NW][4][WAVE];
+  const int tile = blockIdx.y;
+  if (tile >= *n_tiles) return;
+  const int start = tiles[tile * 3], count = tiles[tile * 3 + 1];
+  const int expert = tiles[tile * 3 + 2];
+  const int lane = threadIdx.x % WAVE;
+  const int r = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * MOE_BN;
+
+  const unsigned char* wp[NW];
+  const unsigned char* sp[NW];
+#pragma unroll
+  for (int nb = 0; nb < MOE_NB; ++nb) {
+    const int64_t row = (int64_t)expert * 2 * I + n0 + nb * 16 + r;
+    wp[nb] = w13q + row * (H / 2) + g * (MX_GROUP / 2);
+    sp[nb] = w13s + row * (H / MX_GROUP) + g;
+    wp[MOE_NB + nb] = wp[nb] + (int64_t)I * (H / 2);
+    sp[MOE_NB + nb] = sp[nb] + (int64_t)I * (H / MX_GROUP);
+  }
+  // Rows past count read a valid row instead (count >= 1): the epilogue
+  // stores nothing for them.
+  const short* xp[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int m = mb * 16 + r;
+    const int pair = perm[start + (m < count ? m : 0)];
+    xp[mb] = x + (int64_t)(pair / k) * H + g * MX_GROUP;
+  }
+  mx_gemm_core<MB, NW, mx_gate_up_depth<MB>()>(red, wp, sp, xp, H);
+  gate_up_epilogue<MB>(red, act, start, count, n0, I);
+}
+
+// As moe_down_kernel, on w2q [E, H, I / 2] and w2s [E, H, I / 32].
+template <int MB>
+__global__ __launch_bounds__(MOE_THREADS) void moe_down_mxfp4_kernel(
+    const short* __restrict__ act, const unsigned char* __restrict__ w2q,
+    const unsigned char* __restrict__ w2s, const int32_t* __restrict__ tiles,
+    const int32_t* __restrict__ n_tiles, const int32_t* __restrict__ perm,
+    const float* __restrict__ w, float* __restrict__ y2, int H, int I) {
+  constexpr int NW = MOE_NB;
+  __shared__ float red[MOE_WAVES][MB][NW][4][WAVE];
+  const int tile = blockIdx.y;
+  if (tile >= *n_tiles) return;
+  const int start = tiles[tile * 3], count = tiles[tile * 3 + 1];
+  const int expert = tiles[tile * 3 + 2];
+  const int lane = threadIdx.x % WAVE;
+  const int r = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * MOE_BN;
+
+  const unsigned char* wp[NW];
+  const unsigned char* sp[NW];
+#pragma unroll
+  for (int nb = 0; nb < NW; ++nb) {   // H % 32 == 0: the block is whole
+    const int64_t row = (int64_t)expert * H + n0 + nb * 16 + r;
+    wp[nb] = w2q + row * (I / 2) + g * (MX_GROUP / 2);
+    sp[nb] = w2s + row * (I / MX_GROUP) + g;
+  }
+  const short* xp[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int m = mb * 16 + r;
+    xp[mb] = act + (int64_t)(start + (m < count ? m : 0)) * I + g * MX_GROUP;
+  }
+  mx_gemm_core<MB, NW, mx_down_depth<MB>()>(red, wp, sp, xp, I);
+  down_epilogue<MB>(red, perm, w, y2, start, count, n0, H);
+}
+
+template <int MB>
+void launch_gemms_mxfp4(const MoeFfnMxfp4Args& a, uint32_t n_tiles,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(moe_gate_up_mxfp4_kernel<MB>,
+                     dim3((uint32_t)(a.I / MOE_BN), n_tiles),
+                     dim3(MOE_THREADS), 0, stream, (const short*)a.x,
+                     (const unsigned char*)a.w13q,
+                     (const unsigned char*)a.w13s, a.tiles, a.n_tiles, a.perm,
+                     (short*)a.act, a.H, a.I, a.k);
+  hipLaunchKernelGGL(moe_down_mxfp4_kernel<MB>,
+                     dim3((uint32_t)(a.H / MOE_BN), n_tiles),
+                     dim3(MOE_THREADS), 0, stream, (const short*)a.act,
+                     (const unsigned char*)a.w2q, (const unsigned char*)a.w2s,
+                     a.tiles, a.n_tiles, a.perm, a.w, a.y2, a.H, a.I);
+}
+
 template <int MB>
 void launch_gemms(const MoeFfnArgs& a, uint32_t n_tiles, hipStream_t stream) {
   hipLaunchKernelGGL(moe_gate_up_kernel<MB>,
@@ -522,7 +788,10 @@ hipError_t lds_moe_route(const MoeRouteArgs& a, hipStream_t stream) {
   return hipSuccess;
 }
 
-hipError_t lds_moe_ffn(const MoeFfnArgs& a, hipStream_t stream) {
+// The work list in front of the two GEMMs and the slot sum behind them, for
+// either weight format: A is MoeFfnArgs or MoeFfnMxfp4Args.
+template <class A, class F>
+hipError_t moe_ffn_launch(const A& a, F&& gemms, hipStream_t stream) {
   if (a.T == 0) return hipSuccess;
   const int64_t P = (int64_t)a.T * a.k;
   const uint32_t n_tiles = (uint32_t)moe_tile_bound(P, a.E, a.mb);
@@ -530,12 +799,7 @@ hipError_t lds_moe_ffn(const MoeFfnArgs& a, hipStream_t stream) {
                      stream, a.ids, a.tiles, a.n_tiles, a.perm, (int)P, a.E,
                      16 * a.mb);
   HIP_CHECK_LAST();
-  switch (a.mb) {
-    case 1: launch_gemms<1>(a, n_tiles, stream); break;
-    case 2: launch_gemms<2>(a, n_tiles, stream); break;
-    case 4: launch_gemms<4>(a, n_tiles, stream); break;
-    default: return hipErrorInvalidValue;
-  }
+  if (!gemms(n_tiles)) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
   const int64_t n_oct = (int64_t)a.T * a.H / 8;
   hipLaunchKernelGGL(moe_combine_kernel,
@@ -544,6 +808,27 @@ hipError_t lds_moe_ffn(const MoeFfnArgs& a, hipStream_t stream) {
                      a.H, a.k);
   HIP_CHECK_LAST();
   return hipSuccess;
+}
+
+hipError_t lds_moe_ffn(const MoeFfnArgs& a, hipStream_t stream) {
+  return moe_ffn_launch(a, [&](uint32_t n_tiles) {
+    switch (a.mb) {
+      case 1: launch_gemms<1>(a, n_tiles, stream); return true;
+      case 2: launch_gemms<2>(a, n_tiles, stream); return true;
+      case 4: launch_gemms<4>(a, n_tiles, stream); return true;
+      default: return false;
+    }
+  }, stream);
+}
+
+hipError_t lds_moe_ffn_mxfp4(const MoeFfnMxfp4Args& a, hipStream_t stream) {
+  return moe_ffn_launch(a, [&](uint32_t n_tiles) {
+    switch (a.mb) {
+      case 1: launch_gemms_mxfp4<1>(a, n_tiles, stream); return true;
+      case 2: launch_gemms_mxfp4<2>(a, n_tiles, stream); return true;
+      default: return false;
+    }
+  }, stream);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -811,10 +811,11 @@ std::vector<torch::Tensor> moe_route(torch::Tensor x, torch::Tensor router,
 // the total: act, y2, tiles, n_tiles, perm (MoeFfnArgs).
 struct MoeScratch { int64_t act, y2, tiles, n_tiles, perm, total; };
 
+// mxfp4: the tiles of moe_ffn_mxfp4 (moe_mxfp4_mb) instead of moe_ffn's.
 MoeScratch moe_scratch_layout(int64_t T, int64_t k, int64_t E, int64_t H,
-                              int64_t I) {
+                              int64_t I, bool mxfp4) {
   const int64_t P = T * k;
-  const int mb = moe_mb(P, (int)E);
+  const int mb = mxfp4 ? moe_mxfp4_mb(P, (int)E) : moe_mb(P, (int)E);
   const int64_t n_tiles = moe_tile_bound(P, (int)E, mb);
   const int64_t rows = n_tiles * 16 * mb;
   auto up16 = [](int64_t b) { return (b + 15) / 16 * 16; };
@@ -829,13 +830,38 @@ MoeScratch moe_scratch_layout(int64_t T, int64_t k, int64_t E, int64_t H,
 }
 
 int64_t moe_scratch_bytes(int64_t T, int64_t k, int64_t E, int64_t H,
-                          int64_t I) {
+                          int64_t I, bool mxfp4) {
   check_int(T, 0, INT_MAX / MOE_MAX_TOPK, "T");
   check_int(k, 1, MOE_MAX_TOPK, "k");
   check_int(E, 1, MOE_MAX_EXPERTS, "E");
   check_int(H, 32, INT_MAX, "H");
   check_int(I, 16, INT_MAX, "I");
-  return moe_scratch_layout(T, k, E, H, I).total;
+  return moe_scratch_layout(T, k, E, H, I, mxfp4).total;
+}
+
+// Checks the caller's scratch, or allocates one where there are rows, and
+// points the scratch arrays of a (MoeFfnArgs or MoeFfnMxfp4Args) into it.
+// Returns the buffer, which must outlive the launch's enqueueing.
+template <class A>
+torch::Tensor moe_take_scratch(A& a, const MoeScratch& s,
+                               const c10::optional<torch::Tensor>& scratch,
+                               const torch::Tensor& x) {
+  if (scratch.has_value()) {
+    check_tensor(*scratch, "scratch", x, "x", at::kByte, {ANY});
+    TORCH_CHECK(scratch->size(0) >= s.total, "scratch must hold ", s.total,
+                " bytes, got ", scratch->size(0));
+    check_aligned16(*scratch, "scratch");
+  }
+  if (a.T == 0) return torch::Tensor();
+  torch::Tensor buf = scratch.has_value()
+      ? *scratch : torch::empty({s.total}, x.options().dtype(torch::kByte));
+  uint8_t* base = buf.data_ptr<uint8_t>();
+  a.act = base + s.act;
+  a.y2 = (float*)(base + s.y2);
+  a.tiles = (int32_t*)(base + s.tiles);
+  a.n_tiles = (int32_t*)(base + s.n_tiles);
+  a.perm = (int32_t*)(base + s.perm);
+  return buf;
 }
 
 // y [T, H] = the routed expert FFN of x (MoeFfnArgs). scratch: uint8, at
@@ -864,30 +890,62 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor w13, torch::Tensor w2,
   a.mb = moe_mb(P, a.E);
   check_int(moe_tile_bound(P, a.E, a.mb), 0, GRID_YZ_MAX, "work-list tiles");
   check_int((a.H + 31) / 32, 1, INT_MAX, "column blocks");
-  const MoeScratch s = moe_scratch_layout(a.T, a.k, a.E, a.H, a.I);
-  if (scratch.has_value()) {
-    check_tensor(*scratch, "scratch", x, "x", at::kByte, {ANY});
-    TORCH_CHECK(scratch->size(0) >= s.total, "scratch must hold ", s.total,
-                " bytes, got ", scratch->size(0));
-    check_aligned16(*scratch, "scratch");
-  }
+  const MoeScratch s = moe_scratch_layout(a.T, a.k, a.E, a.H, a.I, false);
   auto y = torch::empty({a.T, a.H}, x.options());
+  torch::Tensor buf = moe_take_scratch(a, s, scratch, x);
   if (a.T == 0) return y;
-  torch::Tensor buf = scratch.has_value()
-      ? *scratch : torch::empty({s.total}, x.options().dtype(torch::kByte));
-  uint8_t* base = buf.data_ptr<uint8_t>();
   a.x = x.data_ptr();
   a.w13 = w13.data_ptr();
   a.w2 = w2.data_ptr();
   a.ids = ids.data_ptr<int32_t>();
   a.w = w.data_ptr<float>();
   a.y = y.data_ptr();
-  a.act = base + s.act;
-  a.y2 = (float*)(base + s.y2);
-  a.tiles = (int32_t*)(base + s.tiles);
-  a.n_tiles = (int32_t*)(base + s.n_tiles);
-  a.perm = (int32_t*)(base + s.perm);
   CHECK_HIP(lds_moe_ffn(a, cur_stream()));
+  return y;
+}
+
+// As moe_ffn on MXFP4 experts (MoeFfnMxfp4Args): w13q [E, 2 I, H / 2], w13s
+// [E, 2 I, H / 32], w2q [E, H, I / 2], w2s [E, H, I / 32], all uint8, H and I
+// multiples of 32. scratch: at least moe_scratch_bytes(..., mxfp4 = true).
+torch::Tensor moe_ffn_mxfp4(torch::Tensor x, torch::Tensor w13q,
+                            torch::Tensor w13s, torch::Tensor w2q,
+                            torch::Tensor w2s, torch::Tensor ids,
+                            torch::Tensor w,
+                            c10::optional<torch::Tensor> scratch) {
+  MoeFfnMxfp4Args a{};
+  a.T = check_moe_x(x);
+  a.H = (int)x.size(1);
+  check_tensor(w13q, "w13q", x, "x", at::kByte, {ANY, ANY, a.H / 2});
+  a.E = check_int(w13q.size(0), 1, MOE_MAX_EXPERTS, "w13q.size(0)");
+  TORCH_CHECK(w13q.size(1) % 64 == 0 && w13q.size(1) >= 64, "w13q.size(1) = "
+              "2 I must be a positive multiple of 64, got ", w13q.size(1));
+  a.I = check_int(w13q.size(1) / 2, 32, INT_MAX, "w13q.size(1) / 2");
+  check_tensor(w13s, "w13s", x, "x", at::kByte, {a.E, 2 * a.I, a.H / 32});
+  check_tensor(w2q, "w2q", x, "x", at::kByte, {a.E, a.H, a.I / 2});
+  check_tensor(w2s, "w2s", x, "x", at::kByte, {a.E, a.H, a.I / 32});
+  check_tensor(ids, "ids", x, "x", at::kInt, {a.T, ANY});
+  a.k = check_int(ids.size(1), 1, std::min<int64_t>(MOE_MAX_TOPK, a.E),
+                  "ids.size(1)");
+  check_tensor(w, "w", x, "x", at::kFloat, {a.T, a.k});
+  check_aligned16(w13q, "w13q");
+  check_aligned16(w2q, "w2q");
+  check_int((int64_t)a.E * 2 * a.I, 1, INT_MAX, "rows of w13q");
+  const int64_t P = (int64_t)a.T * a.k;
+  a.mb = moe_mxfp4_mb(P, a.E);
+  check_int(moe_tile_bound(P, a.E, a.mb), 0, GRID_YZ_MAX, "work-list tiles");
+  const MoeScratch s = moe_scratch_layout(a.T, a.k, a.E, a.H, a.I, true);
+  auto y = torch::empty({a.T, a.H}, x.options());
+  torch::Tensor buf = moe_take_scratch(a, s, scratch, x);
+  if (a.T == 0) return y;
+  a.x = x.data_ptr();
+  a.w13q = w13q.data_ptr();
+  a.w13s = w13s.data_ptr();
+  a.w2q = w2q.data_ptr();
+  a.w2s = w2s.data_ptr();
+  a.ids = ids.data_ptr<int32_t>();
+  a.w = w.data_ptr<float>();
+  a.y = y.data_ptr();
+  CHECK_HIP(lds_moe_ffn_mxfp4(a, cur_stream()));
   return y;
 }
 
@@ -1143,13 +1201,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "w [T, k] fp32)",
         py::arg("x"), py::arg("router"), py::arg("k"), py::arg("renorm"));
   m.def("moe_scratch_bytes", &moe_scratch_bytes,
-        "bytes of scratch moe_ffn needs",
-        py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));
+        "bytes of scratch moe_ffn (with mxfp4: moe_ffn_mxfp4) needs",
+        py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"),
+        py::arg("mxfp4") = false);
   m.def("moe_ffn", &moe_ffn,
         "routed expert FFN: x [T, H], w13 [E, 2 I, H], w2 [E, H, I], ids and "
         "w [T, k] -> y [T, H] bf16",
         py::arg("x"), py::arg("w13"), py::arg("w2"), py::arg("ids"),
         py::arg("w"), py::arg("scratch") = py::none());
+  m.def("moe_ffn_mxfp4", &moe_ffn_mxfp4,
+        "routed expert FFN on MXFP4 experts: x [T, H], w13q [E, 2 I, H / 2], "
+        "w13s [E, 2 I, H / 32], w2q [E, H, I / 2], w2s [E, H, I / 32], ids "
+        "and w [T, k] -> y [T, H] bf16",
+        py::arg("x"), py::arg("w13q"), py::arg("w13s"), py::arg("w2q"),
+        py::arg("w2s"), py::arg("ids"), py::arg("w"),
+        py::arg("scratch") = py::none());
   m.def("sample", &sample,
         "fused temperature/top-k/top-p/seeded sampler with logprobs -> "
         "(tokens, logprobs, n_kept, threshold)",

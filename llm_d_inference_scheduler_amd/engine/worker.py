@@ -415,8 +415,10 @@ class EngineWorker:
         weight-only fp8 with one scale per output channel (DEVELOPMENT.md
         "fp8 weights"), "mxfp4" as OCP Microscaling FP4, e2m1 codes with one
         e8m0 exponent per 32 values along K (DEVELOPMENT.md "MXFP4
-        weights"); "auto" and "bf16" keep the runner's dtype. Both ranks of
-        a P/D pair must use the same value.
+        weights"); "auto" and "bf16" keep the runner's dtype. An MoE model
+        takes "mxfp4" only, which stores its experts as MXFP4 too
+        (DEVELOPMENT.md "Mixture of experts"); the router stays in the
+        runner's dtype. Both ranks of a P/D pair must use the same value.
 
         kv_scales selects the per-head scales of an fp8 KV cache
         (KVPool): "none" (unscaled direct cast), "calibrate" (run

@@ -166,7 +166,8 @@ class LlamaRunner:
         self._fp8_kernel_max_t = 128
         self._mxfp4_kernel_max_t = 128
         self._fp8_scratch: Dict[int, torch.Tensor] = {}
-        # ops.moe_ffn scratch, one per stream, sized by the largest T seen
+        # ops.moe_ffn / ops.moe_ffn_mxfp4 scratch, one per stream, sized by
+        # the largest T seen
         self._moe_scratch: Dict[int, torch.Tensor] = {}
 
     def weight_bytes(self) -> int:
@@ -186,14 +187,26 @@ class LlamaRunner:
         the two are told apart by wq's dtype. Layer by layer, each bf16
         tensor dropped as it is converted. The embedding, lm_head and the
         norms keep the runner's dtype. A quantised runner cannot be
-        converted to another format: the bf16 weights are gone."""
+        converted to another format: the bf16 weights are gone.
+        An MoE model takes "mxfp4" only: wqkv and wo as above, w13 and w2
+        become the pairs (w13q [E, 2 I, H / 2], w13s [E, 2 I, H / 32]) and
+        (w2q [E, H, I / 2], w2s [E, H, I / 32]), converted expert by expert,
+        and the router keeps the runner's dtype. hidden_size and
+        moe_intermediate_size must be multiples of 32, the MX group."""
         if weight_dtype in ("auto", "bf16"):
             return
         if weight_dtype not in ("fp8", "mxfp4"):
             raise ValueError(f"unknown weight_dtype {weight_dtype!r}")
-        if self.cfg.num_experts:
+        c = self.cfg
+        if c.num_experts and weight_dtype != "mxfp4":
             raise ValueError(f"{weight_dtype} weights are not supported for "
-                             "an MoE model: the experts are bf16")
+                             "an MoE model: its experts are bf16 or mxfp4")
+        if c.num_experts and (c.hidden_size % 32 or
+                              c.moe_intermediate_size % 32):
+            raise ValueError(
+                "mxfp4 experts need hidden_size and moe_intermediate_size to "
+                f"be multiples of 32, got {c.hidden_size} and "
+                f"{c.moe_intermediate_size}")
         if self.weight_dtype == weight_dtype:
             return
         if self.weight_dtype != "bf16":
@@ -206,20 +219,28 @@ class LlamaRunner:
             else ops_ref.quantize_weight_mxfp4
         for layer in self.layers:
             for name in LORA_TARGETS:
-                layer[name] = quantize(layer[name])
+                if name in layer:
+                    layer[name] = quantize(layer[name])
+            for name in ("w13", "w2"):
+                if name in layer:
+                    layer[name] = ops_ref.quantize_experts_mxfp4(layer[name])
         self.weight_dtype = weight_dtype
 
     def dense_layers(self) -> List[Dict[str, torch.Tensor]]:
         """self.layers with the four projections as fp32 [in, out] tensors,
         an fp8 or mxfp4 pair dequantised exactly: the weights the forward
-        pass applies."""
+        pass applies. MXFP4 experts come back as fp32 [E, out, in]."""
         def dense(w):
             if not isinstance(w, tuple):
                 return w.float()
             if w[0].dtype == torch.uint8:
                 return ops_ref.dequant_mxfp4_weight(*w, dtype=torch.float32)
             return (w[0].float() * w[1][:, None]).t()
-        return [{k: dense(w) if k in LORA_TARGETS else w
+        def experts(w):
+            return ops_ref.dequant_experts_mxfp4(*w) \
+                if isinstance(w, tuple) else w
+        return [{k: dense(w) if k in LORA_TARGETS else
+                 experts(w) if k in ("w13", "w2") else w
                  for k, w in layer.items()} for layer in self.layers]
 
     # ---- mixture of experts (DEVELOPMENT.md "Mixture of experts") ----
@@ -260,17 +281,22 @@ class LlamaRunner:
         c = self.cfg
         ids, w = ops.moe_route(x, layer["router"], c.experts_per_token,
                                c.norm_topk_prob)
+        mx = isinstance(layer["w13"], tuple)     # MXFP4 pairs
+        if mx:
+            ffn, experts = ops.moe_ffn_mxfp4, (*layer["w13"], *layer["w2"])
+        else:
+            ffn, experts = ops.moe_ffn, (layer["w13"], layer["w2"])
         if not x.is_cuda:
-            return ops.moe_ffn(x, layer["w13"], layer["w2"], ids, w)
+            return ffn(x, *experts, ids, w)
         key = torch.cuda.current_stream(x.device).cuda_stream
         need = ops.moe_scratch_bytes(x.shape[0], c.experts_per_token,
                                      c.num_experts, c.hidden_size,
-                                     c.moe_intermediate_size)
+                                     c.moe_intermediate_size, mxfp4=mx)
         buf = self._moe_scratch.get(key)
         if buf is None or buf.numel() < need:
             buf = self._moe_scratch[key] = torch.empty(
                 need, dtype=torch.uint8, device=x.device)
-        return ops.moe_ffn(x, layer["w13"], layer["w2"], ids, w, buf)
+        return ffn(x, *experts, ids, w, buf)
 
     def _linear(self, x: torch.Tensor, w) -> torch.Tensor:
         """x @ w for a projection of self.layers: dense, an fp8 pair or an
@@ -289,8 +315,8 @@ class LlamaRunner:
         key = torch.cuda.current_stream(x.device).cuda_stream
         buf = self._fp8_scratch.get(key)
         if buf is None:
-            n = max(p[0].numel() for layer in self.layers
-                    for p in layer.values() if isinstance(p, tuple))
+            n = max(layer[name][0].numel() for layer in self.layers
+                    for name in LORA_TARGETS if name in layer)
             buf = self._fp8_scratch[key] = torch.empty(
                 2 * n if mx else n, dtype=torch.bfloat16, device=x.device)
         n_out, n_in = wq.shape[0], x.shape[1]

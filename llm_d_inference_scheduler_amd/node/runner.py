@@ -87,7 +87,8 @@ class NodeConfig:
     kv_cache_dtype: str = "auto"    # auto|bf16|fp8 (fp8 = OCP e4m3 cache)
     # auto|bf16|fp8|mxfp4 (fp8 = weight-only e4m3 projections, a scale per
     # output channel; mxfp4 = e2m1 projections, an e8m0 exponent per 32
-    # values along K); the same on every rank that exchanges KV
+    # values along K, which on an MoE model covers the experts and is the
+    # only quantised choice); the same on every rank that exchanges KV
     weight_dtype: str = "auto"
     # per-head scales of an fp8 cache (engine/worker.py): "none",
     # "calibrate" or the path of a scales JSON. Defaults from the

@@ -289,9 +289,11 @@ def moe_route(x: torch.Tensor, router: torch.Tensor, k: int,
     return ref.moe_route(x, router, k, renorm)
 
 
-def moe_scratch_bytes(T: int, k: int, E: int, H: int, I: int) -> int:
-    """Bytes of the scratch ops.moe_ffn takes for T tokens."""
-    return hip_ops().moe_scratch_bytes(T, k, E, H, I)
+def moe_scratch_bytes(T: int, k: int, E: int, H: int, I: int,
+                      mxfp4: bool = False) -> int:
+    """Bytes of the scratch ops.moe_ffn takes for T tokens; with mxfp4 what
+    ops.moe_ffn_mxfp4 takes (its tiles are at most 32 rows tall)."""
+    return hip_ops().moe_scratch_bytes(T, k, E, H, I, mxfp4)
 
 
 def moe_ffn(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
@@ -306,6 +308,21 @@ def moe_ffn(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
     if _use_hip(x):
         return _ext.moe_ffn(x, w13, w2, ids, w, scratch)
     return ref.moe_ffn(x, w13, w2, ids, w)
+
+
+def moe_ffn_mxfp4(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
+                  w2q: torch.Tensor, w2s: torch.Tensor, ids: torch.Tensor,
+                  w: torch.Tensor,
+                  scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_ffn on MXFP4 experts (DEVELOPMENT.md "Mixture of experts"): w13q
+    [E, 2 I, H / 2], w13s [E, 2 I, H / 32], w2q [E, H, I / 2], w2s
+    [E, H, I / 32], all uint8, the pair of ops.ref.quantize_weight_mxfp4 per
+    expert. y is exactly moe_ffn on the dequantised experts, each of which is
+    a bf16. H % 32 == 0 and I % 32 == 0. scratch (GPU only): at least
+    moe_scratch_bytes(..., mxfp4=True)."""
+    if _use_hip(x):
+        return _ext.moe_ffn_mxfp4(x, w13q, w13s, w2q, w2s, ids, w, scratch)
+    return ref.moe_ffn_mxfp4(x, w13q, w13s, w2q, w2s, ids, w)
 
 
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,

@@ -838,6 +838,33 @@ def moe_ffn(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
     return y.to(x.dtype)
 
 
+def quantize_experts_mxfp4(W: torch.Tensor):
+    """W [E, out, in] -> (wq [E, out, in / 2] uint8, scale [E, out, in / 32]
+    uint8): quantize_weight_mxfp4 expert by expert, so the peak is one
+    expert's fp32 copy."""
+    pairs = [quantize_weight_mxfp4(W[e].t()) for e in range(W.shape[0])]
+    return (torch.stack([p[0] for p in pairs]),
+            torch.stack([p[1] for p in pairs]))
+
+
+def dequant_experts_mxfp4(wq: torch.Tensor, scale: torch.Tensor,
+                          dtype=torch.float32) -> torch.Tensor:
+    """[E, out, in] in `dtype`, exact: every value is zero or a normal bf16."""
+    E, n_out = wq.shape[:2]
+    return _mxfp4_dense_f32(wq.flatten(0, 1), scale.flatten(0, 1)).to(
+        dtype).view(E, n_out, -1)
+
+
+def moe_ffn_mxfp4(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
+                  w2q: torch.Tensor, w2s: torch.Tensor, ids: torch.Tensor,
+                  w: torch.Tensor) -> torch.Tensor:
+    """moe_ffn on the exactly dequantised experts of MXFP4 pairs w13q
+    [E, 2 I, H / 2], w13s [E, 2 I, H / 32], w2q [E, H, I / 2], w2s
+    [E, H, I / 32]."""
+    return moe_ffn(x, dequant_experts_mxfp4(w13q, w13s),
+                   dequant_experts_mxfp4(w2q, w2s), ids, w)
+
+
 _PREFIX_MODEL = PrefixModel()
 hash_prompts = _PREFIX_MODEL.hash_prompts
 table_update = _PREFIX_MODEL.table_update

@@ -41,7 +41,8 @@ def parse_args(argv=None):
                    help="fp8: weight-only e4m3 projections with one scale "
                         "per output channel (half the weight bytes); mxfp4: "
                         "OCP Microscaling FP4 projections, e2m1 with one "
-                        "e8m0 exponent per 32 values (17/64 of the bytes)")
+                        "e8m0 exponent per 32 values (17/64 of the bytes); "
+                        "an MoE model takes mxfp4 only, experts included")
     p.add_argument("--kv-scales", default=None,
                    help='per-head scales of an fp8 KV cache: "none", '
                         '"calibrate" (synthetic tokens at start-up) or the '

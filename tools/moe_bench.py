@@ -1,7 +1,7 @@
 """Microbench of the MoE layer (ops.moe_route + ops.moe_ffn) at
 Qwen3-30B-A3B shapes (results: profiles/moe.md).
 
-    python tools/moe_bench.py [--rounds 7] [--copies 8]
+    python tools/moe_bench.py [--rounds 7] [--copies 8] [--weights mxfp4]
 
 One layer: H 2048, 128 experts of I 768, 8 a token, for T in {1, 16, 64, 256,
 1024, 4096}. Arms, timed in one process in interleaved rounds (arm order
@@ -24,6 +24,15 @@ Reported per arm: the median per-call time over the rounds and the largest
 minus the smallest round, in us; `floor` is the bytes of the router and of
 the experts the calls actually touch (mean over the copies) over 8 TB/s;
 `experts` is that mean count.
+
+--weights mxfp4 (results: profiles/moe_mxfp4.md) quantises every copy's
+experts with ops.ref.quantize_weight_mxfp4 and times two arms instead:
+  mxfp4    ops.moe_route, then ops.moe_ffn_mxfp4 on the MXFP4 pairs
+  bf16     ops.moe_route, then ops.moe_ffn on the dequantised bf16 copy of
+           the same experts: the same function, bit for bit in exact terms
+`floor` is then that of the mxfp4 arm, 4.25 bits a weight (codes and scale
+bytes), and `floor_bf16` the bf16 arm's. The mxfp4 output is checked against
+the float64 bound on the dequantised experts before each T is timed.
 """
 import argparse
 import json
@@ -112,6 +121,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--copies", type=int, default=8)
+    ap.add_argument("--weights", choices=["bf16", "mxfp4"], default="bf16")
     args = ap.parse_args()
     ops.hip_ops()
     c = QWEN3_30B_A3B
@@ -124,6 +134,8 @@ def main():
     w13s = [randn(E, 2 * I, H).mul_(0.02).bfloat16() for _ in range(n)]
     w2s = [randn(E, H, I).mul_(0.02).bfloat16() for _ in range(n)]
     expert_bytes = 3 * I * H * 2
+    if args.weights == "mxfp4":
+        return main_mxfp4(args, routers, w13s, w2s, randn)
     for T in TS:
         xs = [randn(T, H).bfloat16() for _ in range(n)]
         scratch = torch.empty(ops.moe_scratch_bytes(T, k, E, H, I),
@@ -153,6 +165,51 @@ def main():
             T=T, H=H, I=I, E=E, k=k, copies=n, experts=round(touched, 1),
             floor=round((touched * expert_bytes + E * H * 2)
                         / HBM_BYTES_PER_US, 2),
+            **bench(fns, args.rounds))), flush=True)
+        del xs, scratch
+
+
+def main_mxfp4(args, routers, w13s, w2s, randn):
+    n, (E, _, H), I = args.copies, w13s[0].shape, w2s[0].shape[2]
+    k = QWEN3_30B_A3B.experts_per_token
+    ref = ops.ref
+    q13s, q2s = [], []
+    for i in range(n):      # each bf16 copy becomes its own dequantisation
+        q13s.append(ref.quantize_experts_mxfp4(w13s[i]))
+        q2s.append(ref.quantize_experts_mxfp4(w2s[i]))
+        w13s[i] = ref.dequant_experts_mxfp4(*q13s[i], dtype=torch.bfloat16)
+        w2s[i] = ref.dequant_experts_mxfp4(*q2s[i], dtype=torch.bfloat16)
+    weights = 3 * I * H
+    for T in TS:
+        xs = [randn(T, H).bfloat16() for _ in range(n)]
+        scratch = {mx: torch.empty(
+            ops.moe_scratch_bytes(T, k, E, H, I, mxfp4=mx),
+            dtype=torch.uint8, device=DEV) for mx in (True, False)}
+
+        def mxfp4(i):
+            ids, w = ops.moe_route(xs[i], routers[i], k, True)
+            return ops.moe_ffn_mxfp4(xs[i], *q13s[i], *q2s[i], ids, w,
+                                     scratch[True])
+
+        def bf16(i):
+            ids, w = ops.moe_route(xs[i], routers[i], k, True)
+            return ops.moe_ffn(xs[i], w13s[i], w2s[i], ids, w, scratch[False])
+
+        ids, w = ops.moe_route(xs[0], routers[0], k, True)
+        for what, y in (("mxfp4", mxfp4(0)), ("bf16", bf16(0))):
+            excess = moe_cases.ffn_excess(y, xs[0], w13s[0], w2s[0], ids, w)
+            if excess > 0:
+                raise SystemExit(f"T={T} {what}: excess {excess:.3e}")
+            print(f"# T={T} {what} excess {excess:.3e}", flush=True)
+        touched = statistics.mean(
+            int(torch_route(xs[i], routers[i], k)[0].unique().numel())
+            for i in range(n))
+        fns = {"mxfp4": rotating(mxfp4, n), "bf16": rotating(bf16, n)}
+        floor = lambda bits: round(
+            (touched * weights * bits / 8 + E * H * 2) / HBM_BYTES_PER_US, 2)
+        print(json.dumps(dict(
+            T=T, H=H, I=I, E=E, k=k, copies=n, experts=round(touched, 1),
+            floor=floor(4.25), floor_bf16=floor(16),
             **bench(fns, args.rounds))), flush=True)
         del xs, scratch
 
