@@ -326,6 +326,31 @@ struct MoeFfnMxfp4Args {
 
 hipError_t lds_moe_ffn_mxfp4(const MoeFfnMxfp4Args& a, hipStream_t stream);
 
+// moe_ffn on fp8 experts: e4m3 (OCP) weights with one fp32 scale per expert
+// and output channel. The scales are applied to the fp32 sums, never to the
+// weights: act = bf16(silu(w13s[e, n] * sum_g) * (w13s[e, I + n] * sum_u)),
+// y2 = (w2s[e, n] * sum) * w[pair]. The tiles are those of MoeFfnArgs.
+struct MoeFfnFp8Args {
+  const void* x;        // [T, H] bf16, H % 32 == 0, 16-byte aligned
+  const void* w13q;     // [E, 2 I, H] e4m3, 16-byte aligned, I % 16 == 0
+  const float* w13s;    // [E, 2 I], 16-byte aligned
+  const void* w2q;      // [E, H, I] e4m3, 16-byte aligned
+  const float* w2s;     // [E, H], 16-byte aligned
+  const int32_t* ids;   // [T, k]
+  const float* w;       // [T, k]
+  void* y;              // [T, H] bf16
+  // scratch as in MoeFfnArgs
+  void* act;
+  float* y2;
+  int32_t* tiles;
+  int32_t* n_tiles;
+  int32_t* perm;
+  int T, H, I, E, k;
+  int mb;               // moe_mb(T * k, E)
+};
+
+hipError_t lds_moe_ffn_fp8(const MoeFfnFp8Args& a, hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

@@ -38,6 +38,7 @@
 // index or on the other rows of the launch.
 #include "hip_common.h"
 #include "launchers.h"
+#include "fp8_convert.h"
 
 // The device code of this file is built without packed fp32 arithmetic
 // (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32): some forms of these
@@ -55,21 +56,9 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
 constexpr int LIN_THREADS = 256;
 constexpr int LIN_WAVES = LIN_THREADS / WAVE;
 constexpr int LIN_ROWS = 64;   // rows of a grid.y tile
-
-// 8 e4m3 bytes (two dwords) -> the 8 bf16 of one MFMA operand, in byte order
-__device__ __forceinline__ short8 fp8x8_to_bf16(uint32_t lo, uint32_t hi) {
-  union { bf16x2 h[4]; short8 s; } u;
-  u.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
-  u.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
-  u.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
-  u.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
-  return u.s;
-}
 
 // One ring stage: a K block's weights (16 bytes per column block) and x
 // (2 x 16 bytes per row block) of this lane.

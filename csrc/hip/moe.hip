@@ -64,6 +64,37 @@
 //     and its weights come from L2 after the first. A pair's bits do not
 //     depend on that choice either.
 //
+// fp8 experts (moe_ffn_fp8): w13q [E, 2 I, H] and w2q [E, H, I] OCP e4m3, and
+// w13s [E, 2 I], w2s [E, H] fp32, one scale per expert and output channel:
+// the pair of ops.ref.quantize_weight_fp8 per expert. Everything else is as
+// for bf16 experts, tile heights (moe_mb) and scratch included.
+//   moe_gate_up_fp8_kernel<MB>, moe_down_fp8_kernel<MB>   the same grids.
+//     What changes is the K loop (fp8_gemm_core): its unit is that of
+//     linear_fp8_kernel. A stage is a 64-wide K block; lane group
+//     g = lane >> 4 owns k = 64 b + 16 g .. + 15 of it. One 16-byte load is
+//     those 16 bytes of weight row lane & 15, two 16-byte loads are the
+//     lane's x row at the same k. Bytes 0..7 and 8..15 go through
+//     v_cvt_scalef32_pk_bf16_fp8 with scale 1, which is exact, and are the B
+//     operands of two MFMAs; x is read in the same order, so the k order
+//     inside a step is permuted alike on both operands. The waves take the K
+//     blocks round-robin, a register ring keeps the next DEPTH blocks in
+//     flight, and the accumulators meet in LDS as above. Every weight byte is
+//     read once, as fp8, by the one wave that uses it.
+//   K tail. K % 16 == 0 is all that is asked (H % 32 and I % 16, as for bf16
+//     experts). The last K block may hold one to three lane groups: a lane
+//     group past K issues no load and feeds zeros on both operands. The
+//     straight-line turns of the ring cover whole blocks only and carry no
+//     predicate.
+//   Scales. In the epilogues only, in this order. Gate-up: the fp32 sums of
+//     gate column n and up column n times w13s[e, n] and w13s[e, I + n], then
+//     silu(g) * u and the one bf16 rounding of act. Down: the fp32 sum times
+//     w2s[e, n], then times the pair's routing weight, stored fp32 in y2.
+//   Tile height. A stage is 4 NW + 8 MB registers a lane: 24 / 32 / 48 for
+//     gate-up at MB 1 / 2 / 4, 16 / 24 / 40 for down. MB 4 fits next to 64
+//     accumulators with a ring of two stages (three for down), without
+//     scratch, so nothing is capped. The depths are register arithmetic, not
+//     swept.
+//
 // Determinism: no atomic touches floating-point data. The bits of a pair
 // depend on its x row, its expert and its routing weight only: MFMA rows and
 // columns never mix, the K step -> wave assignment depends on K alone and
@@ -71,6 +102,7 @@
 // the pair's position in its segment or on the other rows of the launch.
 #include "hip_common.h"
 #include "launchers.h"
+#include "fp8_convert.h"
 #include "mxfp4_convert.h"
 
 // Built without packed fp32 arithmetic, as linear_fp8.hip is and for the
@@ -398,19 +430,31 @@ __device__ __forceinline__ f32x4 red_sum(
   return s;
 }
 
-// The epilogues, shared by the bf16 and the MXFP4 kernels. Gate-up: act =
-// bf16(silu(gate) * up) for the tile's live rows, by sorted position.
-template <int MB>
+// The epilogues, shared by the bf16, the MXFP4 and the fp8 kernels. Gate-up:
+// act = bf16(silu(gate) * up) for the tile's live rows, by sorted position.
+// SCALED (fp8 experts): sc is the expert's row of w13s, and the fp32 sums of
+// gate column n and up column n are multiplied by sc[n] and sc[I + n] first.
+template <int MB, bool SCALED = false>
 __device__ __forceinline__ void gate_up_epilogue(
     const float (&red)[MOE_WAVES][MB][2 * MOE_NB][4][WAVE],
-    short* __restrict__ act, int start, int count, int n0, int I) {
+    short* __restrict__ act, int start, int count, int n0, int I,
+    const float* __restrict__ sc = nullptr) {
   constexpr int NW = 2 * MOE_NB;
   for (int i = threadIdx.x; i < count * (MOE_BN / 4); i += MOE_THREADS) {
     const int m = i / (MOE_BN / 4), c = (i % (MOE_BN / 4)) * 4;
     const int n = n0 + c;
     if (n >= I) continue;  // I % 16 == 0: four columns are in or out
-    const f32x4 g = red_sum<MB, NW>(red, m, c >> 4, c & 15);
-    const f32x4 u = red_sum<MB, NW>(red, m, MOE_NB + (c >> 4), c & 15);
+    f32x4 g = red_sum<MB, NW>(red, m, c >> 4, c & 15);
+    f32x4 u = red_sum<MB, NW>(red, m, MOE_NB + (c >> 4), c & 15);
+    if (SCALED) {
+      const f32x4 sg = *(const f32x4*)(sc + n);
+      const f32x4 su = *(const f32x4*)(sc + I + n);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        g[e] *= sg[e];
+        u[e] *= su[e];
+      }
+    }
     short4v o;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
@@ -419,12 +463,15 @@ __device__ __forceinline__ void gate_up_epilogue(
   }
 }
 
-// Down: y2[pair] = the pair's routing weight times its row, fp32.
-template <int MB>
+// Down: y2[pair] = the pair's routing weight times its row, fp32. SCALED (fp8
+// experts): sc is the expert's row of w2s, and the fp32 sum of column n is
+// multiplied by sc[n] first, then by the routing weight.
+template <int MB, bool SCALED = false>
 __device__ __forceinline__ void down_epilogue(
     const float (&red)[MOE_WAVES][MB][MOE_NB][4][WAVE],
     const int32_t* __restrict__ perm, const float* __restrict__ w,
-    float* __restrict__ y2, int start, int count, int n0, int H) {
+    float* __restrict__ y2, int start, int count, int n0, int H,
+    const float* __restrict__ sc = nullptr) {
   for (int i = threadIdx.x; i < count * (MOE_BN / 4); i += MOE_THREADS) {
     const int m = i / (MOE_BN / 4), c = (i % (MOE_BN / 4)) * 4;
     const int n = n0 + c;
@@ -432,6 +479,11 @@ __device__ __forceinline__ void down_epilogue(
     const int pair = perm[start + m];
     const float wt = w[pair];
     f32x4 s = red_sum<MB, MOE_NB>(red, m, c >> 4, c & 15);
+    if (SCALED) {
+      const f32x4 sn = *(const f32x4*)(sc + n);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] *= sn[e];
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e) s[e] *= wt;
     *(f32x4*)(y2 + (int64_t)pair * H + n) = s;
@@ -745,6 +797,217 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_down_mxfp4_kernel(
   down_epilogue<MB>(red, perm, w, y2, start, count, n0, H);
 }
 
+// ---- the two expert GEMMs on fp8 experts -----------------------------------
+
+constexpr int F8_GROUP = 16;     // k of one lane group: a 16-byte weight load
+constexpr int F8_KBLOCK = 64;    // k of one stage: a group a lane group
+
+// One ring stage of this lane: per weight row block 16 e4m3 bytes, per x row
+// block the 16 bf16 of the same k.
+template <int MB, int NW>
+struct F8Stage {
+  u32x4 w[NW];
+  short8 x[MB][2];
+};
+
+// K block kb of this lane's group. KPRED: groups_left = K / 16 - (lane >> 4),
+// and a lane group whose k is past K issues no load and feeds zeros on both
+// operands (byte 0 is +0). Otherwise the block is whole.
+template <int MB, int NW, bool KPRED>
+__device__ __forceinline__ void f8_load_stage(
+    F8Stage<MB, NW>& s, const unsigned char* const (&wp)[NW],
+    const short* const (&xp)[MB], int kb, int groups_left) {
+  const bool ok = !KPRED || kb * (F8_KBLOCK / F8_GROUP) < groups_left;
+  const u32x4 zw = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int n = 0; n < NW; ++n)
+    s.w[n] = ok ? *(const u32x4*)(wp[n] + kb * F8_KBLOCK) : zw;
+#pragma unroll
+  for (int m = 0; m < MB; ++m) {
+    s.x[m][0] = load8_or_zero(xp[m] + kb * F8_KBLOCK, ok);
+    s.x[m][1] = load8_or_zero(xp[m] + kb * F8_KBLOCK + 8, ok);
+  }
+}
+
+// One turn of the ring, as ring_round: bytes 0..7 of a stage's weights are
+// the B operand of one MFMA and bytes 8..15 of the next, against the lane's x
+// at the same k. TAIL = false runs on whole K blocks only: neither the stage
+// count nor K is checked.
+template <int MB, int NW, int DEPTH, bool TAIL>
+__device__ __forceinline__ void f8_ring_round(
+    F8Stage<MB, NW> (&ring)[DEPTH], f32x4 (&acc)[MB][NW],
+    const unsigned char* const (&wp)[NW], const short* const (&xp)[MB],
+    int wave, int groups_left, int i, int n_it) {
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) {
+    if (TAIL && i + d >= n_it) break;
+#pragma unroll
+    for (int n = 0; n < NW; ++n) {
+      const short8 b0 = fp8x8_to_bf16(ring[d].w[n][0], ring[d].w[n][1]);
+      const short8 b1 = fp8x8_to_bf16(ring[d].w[n][2], ring[d].w[n][3]);
+#pragma unroll
+      for (int m = 0; m < MB; ++m) {
+        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            ring[d].x[m][0], b0, acc[m][n], 0, 0, 0);
+        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            ring[d].x[m][1], b1, acc[m][n], 0, 0, 0);
+      }
+    }
+    if (!TAIL || i + d + DEPTH < n_it)
+      f8_load_stage<MB, NW, TAIL>(ring[d], wp, xp,
+                                  wave + (i + d + DEPTH) * MOE_WAVES,
+                                  groups_left);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// gemm_core for e4m3 weight rows: this wave's 64-wide K blocks (wave,
+// wave + 4, ... below ceil(K / 64)), then all four waves' accumulators into
+// red. wp and xp point at this lane's group of K block 0 of each row.
+// K % 16 == 0; the last block may hold one to three groups. n_full counts
+// this wave's blocks below floor(K / 64): the straight-line turns stay inside
+// them, so only the last turns carry the K predicate.
+template <int MB, int NW, int DEPTH>
+__device__ __forceinline__ void fp8_gemm_core(
+    float (&red)[MOE_WAVES][MB][NW][4][WAVE],
+    const unsigned char* const (&wp)[NW], const short* const (&xp)[MB],
+    int K) {
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+  const int groups_left = K / F8_GROUP - (lane >> 4);
+  f32x4 acc[MB][NW];
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int n = 0; n < NW; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int n_kb = (K + F8_KBLOCK - 1) / F8_KBLOCK;
+  const int n_it = (n_kb - wave + MOE_WAVES - 1) / MOE_WAVES;  // may be 0
+  const int n_full = (K / F8_KBLOCK - wave + MOE_WAVES - 1) / MOE_WAVES;
+  F8Stage<MB, NW> ring[DEPTH];
+  int i = 0;
+  if (n_full >= 2 * DEPTH) {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) {
+      f8_load_stage<MB, NW, false>(ring[d], wp, xp, wave + d * MOE_WAVES,
+                                   groups_left);
+      __builtin_amdgcn_sched_barrier(0);  // issue the stages in ring order
+    }
+    for (; i + 2 * DEPTH <= n_full; i += DEPTH)
+      f8_ring_round<MB, NW, DEPTH, false>(ring, acc, wp, xp, wave,
+                                          groups_left, i, n_it);
+  } else {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d)
+      if (d < n_it)
+        f8_load_stage<MB, NW, true>(ring[d], wp, xp, wave + d * MOE_WAVES,
+                                    groups_left);
+  }
+  for (; i < n_it; i += DEPTH)
+    f8_ring_round<MB, NW, DEPTH, true>(ring, acc, wp, xp, wave, groups_left,
+                                       i, n_it);
+
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int n = 0; n < NW; ++n)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) red[wave][m][n][j][lane] = acc[m][n][j];
+  __syncthreads();
+}
+
+// ring depth by registers: a stage holds 4 NW + 8 MB a lane. Gate-up (NW 4):
+// 24 / 32 / 48 at MB 1 / 2 / 4 next to 16 MB accumulators; down (NW 2):
+// 16 / 24 / 40 next to 8 MB. Chosen by that arithmetic, not swept.
+template <int MB>
+constexpr int f8_gate_up_depth() { return MB == 1 ? 4 : MB == 2 ? 3 : 2; }
+template <int MB>
+constexpr int f8_down_depth() { return MB == 4 ? 3 : 4; }
+
+// As moe_gate_up_kernel, on w13q [E, 2 I, H] e4m3 and w13s [E, 2 I] fp32.
+template <int MB>
+__global__ __launch_bounds__(MOE_THREADS) void moe_gate_up_fp8_kernel(
+    const short* __restrict__ x, const unsigned char* __restrict__ w13q,
+    const float* __restrict__ w13s, const int32_t* __restrict__ tiles,
+    const int32_t* __restrict__ n_tiles, const int32_t* __restrict__ perm,
+    short* __restrict__ act, int H, int I, int k) {
+  constexpr int NW = 2 * MOE_NB;   // gate blocks, then up blocks
+  __shared__ float red[MOE_WAVES][MB][NW][4][WAVE];
+  const int tile = blockIdx.y;
+  if (tile >= *n_tiles) return;
+  const int start = tiles[tile * 3], count = tiles[tile * 3 + 1];
+  const int expert = tiles[tile * 3 + 2];
+  const int lane = threadIdx.x % WAVE;
+  const int r = lane & 15, kq = (lane >> 4) * F8_GROUP;
+  const int n0 = blockIdx.x * MOE_BN;
+
+  // Rows past count and column blocks past I read a valid row instead
+  // (count >= 1, n0 < I): the epilogue stores nothing for them.
+  const unsigned char* wp[NW];
+#pragma unroll
+  for (int nb = 0; nb < MOE_NB; ++nb) {
+    const int n = n0 + nb * 16 < I ? n0 + nb * 16 + r : n0 + r;
+    wp[nb] = w13q + ((int64_t)expert * 2 * I + n) * H + kq;
+    wp[MOE_NB + nb] = wp[nb] + (int64_t)I * H;
+  }
+  const short* xp[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int m = mb * 16 + r;
+    const int pair = perm[start + (m < count ? m : 0)];
+    xp[mb] = x + (int64_t)(pair / k) * H + kq;
+  }
+  fp8_gemm_core<MB, NW, f8_gate_up_depth<MB>()>(red, wp, xp, H);
+  gate_up_epilogue<MB, true>(red, act, start, count, n0, I,
+                             w13s + (int64_t)expert * 2 * I);
+}
+
+// As moe_down_kernel, on w2q [E, H, I] e4m3 and w2s [E, H] fp32.
+template <int MB>
+__global__ __launch_bounds__(MOE_THREADS) void moe_down_fp8_kernel(
+    const short* __restrict__ act, const unsigned char* __restrict__ w2q,
+    const float* __restrict__ w2s, const int32_t* __restrict__ tiles,
+    const int32_t* __restrict__ n_tiles, const int32_t* __restrict__ perm,
+    const float* __restrict__ w, float* __restrict__ y2, int H, int I) {
+  constexpr int NW = MOE_NB;
+  __shared__ float red[MOE_WAVES][MB][NW][4][WAVE];
+  const int tile = blockIdx.y;
+  if (tile >= *n_tiles) return;
+  const int start = tiles[tile * 3], count = tiles[tile * 3 + 1];
+  const int expert = tiles[tile * 3 + 2];
+  const int lane = threadIdx.x % WAVE;
+  const int r = lane & 15, kq = (lane >> 4) * F8_GROUP;
+  const int n0 = blockIdx.x * MOE_BN;
+
+  const unsigned char* wp[NW];
+#pragma unroll
+  for (int nb = 0; nb < NW; ++nb)   // H % 32 == 0: the block is whole
+    wp[nb] = w2q + ((int64_t)expert * H + n0 + nb * 16 + r) * I + kq;
+  const short* xp[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int m = mb * 16 + r;
+    xp[mb] = act + (int64_t)(start + (m < count ? m : 0)) * I + kq;
+  }
+  fp8_gemm_core<MB, NW, f8_down_depth<MB>()>(red, wp, xp, I);
+  down_epilogue<MB, true>(red, perm, w, y2, start, count, n0, H,
+                          w2s + (int64_t)expert * H);
+}
+
+template <int MB>
+void launch_gemms_fp8(const MoeFfnFp8Args& a, uint32_t n_tiles,
+                      hipStream_t stream) {
+  hipLaunchKernelGGL(moe_gate_up_fp8_kernel<MB>,
+                     dim3((uint32_t)((a.I + MOE_BN - 1) / MOE_BN), n_tiles),
+                     dim3(MOE_THREADS), 0, stream, (const short*)a.x,
+                     (const unsigned char*)a.w13q, a.w13s, a.tiles, a.n_tiles,
+                     a.perm, (short*)a.act, a.H, a.I, a.k);
+  hipLaunchKernelGGL(moe_down_fp8_kernel<MB>,
+                     dim3((uint32_t)(a.H / MOE_BN), n_tiles),
+                     dim3(MOE_THREADS), 0, stream, (const short*)a.act,
+                     (const unsigned char*)a.w2q, a.w2s, a.tiles, a.n_tiles,
+                     a.perm, a.w, a.y2, a.H, a.I);
+}
+
 template <int MB>
 void launch_gemms_mxfp4(const MoeFfnMxfp4Args& a, uint32_t n_tiles,
                         hipStream_t stream) {
@@ -789,7 +1052,7 @@ hipError_t lds_moe_route(const MoeRouteArgs& a, hipStream_t stream) {
 }
 
 // The work list in front of the two GEMMs and the slot sum behind them, for
-// either weight format: A is MoeFfnArgs or MoeFfnMxfp4Args.
+// any weight format: A is MoeFfnArgs, MoeFfnMxfp4Args or MoeFfnFp8Args.
 template <class A, class F>
 hipError_t moe_ffn_launch(const A& a, F&& gemms, hipStream_t stream) {
   if (a.T == 0) return hipSuccess;
@@ -826,6 +1089,17 @@ hipError_t lds_moe_ffn_mxfp4(const MoeFfnMxfp4Args& a, hipStream_t stream) {
     switch (a.mb) {
       case 1: launch_gemms_mxfp4<1>(a, n_tiles, stream); return true;
       case 2: launch_gemms_mxfp4<2>(a, n_tiles, stream); return true;
+      default: return false;
+    }
+  }, stream);
+}
+
+hipError_t lds_moe_ffn_fp8(const MoeFfnFp8Args& a, hipStream_t stream) {
+  return moe_ffn_launch(a, [&](uint32_t n_tiles) {
+    switch (a.mb) {
+      case 1: launch_gemms_fp8<1>(a, n_tiles, stream); return true;
+      case 2: launch_gemms_fp8<2>(a, n_tiles, stream); return true;
+      case 4: launch_gemms_fp8<4>(a, n_tiles, stream); return true;
       default: return false;
     }
   }, stream);

@@ -840,7 +840,8 @@ int64_t moe_scratch_bytes(int64_t T, int64_t k, int64_t E, int64_t H,
 }
 
 // Checks the caller's scratch, or allocates one where there are rows, and
-// points the scratch arrays of a (MoeFfnArgs or MoeFfnMxfp4Args) into it.
+// points the scratch arrays of a (MoeFfnArgs, MoeFfnMxfp4Args or
+// MoeFfnFp8Args) into it.
 // Returns the buffer, which must outlive the launch's enqueueing.
 template <class A>
 torch::Tensor moe_take_scratch(A& a, const MoeScratch& s,
@@ -946,6 +947,55 @@ torch::Tensor moe_ffn_mxfp4(torch::Tensor x, torch::Tensor w13q,
   a.w = w.data_ptr<float>();
   a.y = y.data_ptr();
   CHECK_HIP(lds_moe_ffn_mxfp4(a, cur_stream()));
+  return y;
+}
+
+// As moe_ffn on fp8 experts (MoeFfnFp8Args): w13q [E, 2 I, H] and w2q
+// [E, H, I] float8_e4m3fn, w13s [E, 2 I] and w2s [E, H] fp32, one scale per
+// expert and output channel, applied to the fp32 sums. H % 32 == 0 and
+// I % 16 == 0 as for moe_ffn, whose tiles and scratch (moe_scratch_bytes)
+// these are.
+torch::Tensor moe_ffn_fp8(torch::Tensor x, torch::Tensor w13q,
+                          torch::Tensor w13s, torch::Tensor w2q,
+                          torch::Tensor w2s, torch::Tensor ids,
+                          torch::Tensor w,
+                          c10::optional<torch::Tensor> scratch) {
+  MoeFfnFp8Args a{};
+  a.T = check_moe_x(x);
+  a.H = (int)x.size(1);
+  check_tensor(w13q, "w13q", x, "x", at::kFloat8_e4m3fn, {ANY, ANY, a.H});
+  a.E = check_int(w13q.size(0), 1, MOE_MAX_EXPERTS, "w13q.size(0)");
+  TORCH_CHECK(w13q.size(1) % 32 == 0 && w13q.size(1) >= 32, "w13q.size(1) = "
+              "2 I must be a positive multiple of 32, got ", w13q.size(1));
+  a.I = check_int(w13q.size(1) / 2, 16, INT_MAX, "w13q.size(1) / 2");
+  check_tensor(w13s, "w13s", x, "x", at::kFloat, {a.E, 2 * a.I});
+  check_tensor(w2q, "w2q", x, "x", at::kFloat8_e4m3fn, {a.E, a.H, a.I});
+  check_tensor(w2s, "w2s", x, "x", at::kFloat, {a.E, a.H});
+  check_tensor(ids, "ids", x, "x", at::kInt, {a.T, ANY});
+  a.k = check_int(ids.size(1), 1, std::min<int64_t>(MOE_MAX_TOPK, a.E),
+                  "ids.size(1)");
+  check_tensor(w, "w", x, "x", at::kFloat, {a.T, a.k});
+  check_aligned16(w13q, "w13q");
+  check_aligned16(w13s, "w13s");
+  check_aligned16(w2q, "w2q");
+  check_aligned16(w2s, "w2s");
+  check_int((int64_t)a.E * 2 * a.I, 1, INT_MAX, "rows of w13q");
+  const int64_t P = (int64_t)a.T * a.k;
+  a.mb = moe_mb(P, a.E);
+  check_int(moe_tile_bound(P, a.E, a.mb), 0, GRID_YZ_MAX, "work-list tiles");
+  const MoeScratch s = moe_scratch_layout(a.T, a.k, a.E, a.H, a.I, false);
+  auto y = torch::empty({a.T, a.H}, x.options());
+  torch::Tensor buf = moe_take_scratch(a, s, scratch, x);
+  if (a.T == 0) return y;
+  a.x = x.data_ptr();
+  a.w13q = w13q.data_ptr();
+  a.w13s = w13s.data_ptr<float>();
+  a.w2q = w2q.data_ptr();
+  a.w2s = w2s.data_ptr<float>();
+  a.ids = ids.data_ptr<int32_t>();
+  a.w = w.data_ptr<float>();
+  a.y = y.data_ptr();
+  CHECK_HIP(lds_moe_ffn_fp8(a, cur_stream()));
   return y;
 }
 
@@ -1212,6 +1262,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_ffn_mxfp4", &moe_ffn_mxfp4,
         "routed expert FFN on MXFP4 experts: x [T, H], w13q [E, 2 I, H / 2], "
         "w13s [E, 2 I, H / 32], w2q [E, H, I / 2], w2s [E, H, I / 32], ids "
+        "and w [T, k] -> y [T, H] bf16",
+        py::arg("x"), py::arg("w13q"), py::arg("w13s"), py::arg("w2q"),
+        py::arg("w2s"), py::arg("ids"), py::arg("w"),
+        py::arg("scratch") = py::none());
+  m.def("moe_ffn_fp8", &moe_ffn_fp8,
+        "routed expert FFN on fp8 experts: x [T, H], w13q [E, 2 I, H] and "
+        "w2q [E, H, I] float8_e4m3fn, w13s [E, 2 I] and w2s [E, H] fp32, ids "
         "and w [T, k] -> y [T, H] bf16",
         py::arg("x"), py::arg("w13q"), py::arg("w13s"), py::arg("w2q"),
         py::arg("w2s"), py::arg("ids"), py::arg("w"),

@@ -410,7 +410,8 @@ class EngineWorker:
                  kv_calib_tokens: int = 2048,
                  max_loras: int = 0,
                  max_lora_rank: int = 16,
-                 weight_dtype: str = "auto"):
+                 weight_dtype: str = "auto",
+                 expert_dtype: str = "auto"):
         """weight_dtype "fp8" stores the four projections of every layer as
         weight-only fp8 with one scale per output channel (DEVELOPMENT.md
         "fp8 weights"), "mxfp4" as OCP Microscaling FP4, e2m1 codes with one
@@ -419,6 +420,13 @@ class EngineWorker:
         takes "mxfp4" only, which stores its experts as MXFP4 too
         (DEVELOPMENT.md "Mixture of experts"); the router stays in the
         runner's dtype. Both ranks of a P/D pair must use the same value.
+
+        expert_dtype "bf16", "fp8" or "mxfp4" (MoE models only) gives the
+        experts that format whatever weight_dtype says, and weight_dtype
+        then governs wqkv and wo alone: "fp8" with weight_dtype "fp8" is the
+        all-fp8 MoE model, "mxfp4" with weight_dtype "auto" MXFP4 experts
+        under bf16 attention. "auto" is the rule above, under which
+        weight_dtype "fp8" alone on an MoE model is an error.
 
         kv_scales selects the per-head scales of an fp8 KV cache
         (KVPool): "none" (unscaled direct cast), "calibrate" (run
@@ -437,6 +445,11 @@ class EngineWorker:
         if config.num_experts and max_loras > 0:
             raise ValueError("LoRA adapters are not supported for an MoE "
                              "model (max_loras must be 0)")
+        if expert_dtype not in ("auto", "bf16", "fp8", "mxfp4"):
+            raise ValueError(f"unknown expert_dtype {expert_dtype!r}")
+        if expert_dtype != "auto" and not config.num_experts:
+            raise ValueError(f"expert_dtype {expert_dtype!r} needs an MoE "
+                             "model: a dense model has no experts")
         self.cfg = config
         self.device = torch.device(device)
         self._is_cuda_dev = lambda: self.device.type == "cuda"
@@ -463,7 +476,12 @@ class EngineWorker:
         self.mgr = BlockManager(kv_blocks, self.pool.block_size,
                                 prefix_caching=prefix_caching)
         self.model = LlamaRunner(config, self.device, dtype, seed=seed)
-        self.model.quantize_weights(weight_dtype)
+        if expert_dtype == "auto":
+            self.model.quantize_weights(weight_dtype)
+        else:
+            self.model.quantize_weights(weight_dtype, experts=False)
+            if expert_dtype != "bf16":
+                self.model.quantize_experts(expert_dtype)
         self.seed = seed
         self.max_loras = max_loras
         self.adapters: Dict[str, LoraAdapter] = {}   # registered, on the host

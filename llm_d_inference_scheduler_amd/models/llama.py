@@ -163,10 +163,11 @@ class LlamaRunner:
         # through a dequantised bf16 copy and torch.matmul (crossovers:
         # profiles/linear_fp8.md, profiles/linear_mxfp4.md)
         self.weight_dtype = "bf16"
+        self.expert_dtype = "bf16"     # w13 and w2 (quantize_experts)
         self._fp8_kernel_max_t = 128
         self._mxfp4_kernel_max_t = 128
         self._fp8_scratch: Dict[int, torch.Tensor] = {}
-        # ops.moe_ffn / ops.moe_ffn_mxfp4 scratch, one per stream, sized by
+        # ops.moe_ffn / moe_ffn_mxfp4 / moe_ffn_fp8 scratch, one per stream, sized by
         # the largest T seen
         self._moe_scratch: Dict[int, torch.Tensor] = {}
 
@@ -178,7 +179,8 @@ class LlamaRunner:
         return sum(t.numel() * t.element_size() for t in tensors)
 
     # ---- quantised weights (DEVELOPMENT.md "fp8 weights", "MXFP4 weights")
-    def quantize_weights(self, weight_dtype: str) -> None:
+    def quantize_weights(self, weight_dtype: str,
+                         experts: bool = True) -> None:
         """Convert the four projections of every layer in place to a
         weight-only format. "fp8": layer[name] becomes the pair (wq
         [out, in] float8_e4m3fn, scale [out] fp32) of
@@ -188,25 +190,23 @@ class LlamaRunner:
         tensor dropped as it is converted. The embedding, lm_head and the
         norms keep the runner's dtype. A quantised runner cannot be
         converted to another format: the bf16 weights are gone.
-        An MoE model takes "mxfp4" only: wqkv and wo as above, w13 and w2
-        become the pairs (w13q [E, 2 I, H / 2], w13s [E, 2 I, H / 32]) and
-        (w2q [E, H, I / 2], w2s [E, H, I / 32]), converted expert by expert,
-        and the router keeps the runner's dtype. hidden_size and
-        moe_intermediate_size must be multiples of 32, the MX group."""
+        On an MoE model the experts go with the projections, and "mxfp4" is
+        the only format this takes: wqkv and wo as above, w13 and w2 as
+        quantize_experts("mxfp4") leaves them, and the router keeps the
+        runner's dtype. experts=False converts wqkv and wo alone, in either
+        format, and leaves the experts to quantize_experts."""
         if weight_dtype in ("auto", "bf16"):
             return
         if weight_dtype not in ("fp8", "mxfp4"):
             raise ValueError(f"unknown weight_dtype {weight_dtype!r}")
-        c = self.cfg
-        if c.num_experts and weight_dtype != "mxfp4":
-            raise ValueError(f"{weight_dtype} weights are not supported for "
-                             "an MoE model: its experts are bf16 or mxfp4")
-        if c.num_experts and (c.hidden_size % 32 or
-                              c.moe_intermediate_size % 32):
+        experts = experts and bool(self.cfg.num_experts)
+        if experts and weight_dtype != "mxfp4":
             raise ValueError(
-                "mxfp4 experts need hidden_size and moe_intermediate_size to "
-                f"be multiples of 32, got {c.hidden_size} and "
-                f"{c.moe_intermediate_size}")
+                f"weight_dtype {weight_dtype!r} alone is not supported for an "
+                f"MoE model: pass expert_dtype={weight_dtype!r} to quantise "
+                "its experts as well")
+        if experts:
+            self._check_expert_dtype(weight_dtype, self.weight_dtype)
         if self.weight_dtype == weight_dtype:
             return
         if self.weight_dtype != "bf16":
@@ -221,15 +221,56 @@ class LlamaRunner:
             for name in LORA_TARGETS:
                 if name in layer:
                     layer[name] = quantize(layer[name])
-            for name in ("w13", "w2"):
-                if name in layer:
-                    layer[name] = ops_ref.quantize_experts_mxfp4(layer[name])
         self.weight_dtype = weight_dtype
+        if experts:
+            self.quantize_experts(weight_dtype)
+
+    def _check_expert_dtype(self, expert_dtype: str, allowed: str) -> None:
+        """ValueError unless the experts can become expert_dtype: an MoE model
+        whose experts are still bf16 (or, from quantize_weights on a runner
+        it has converted before, already `allowed`)."""
+        c = self.cfg
+        if expert_dtype not in ("fp8", "mxfp4"):
+            raise ValueError(f"unknown expert_dtype {expert_dtype!r}")
+        if not c.num_experts:
+            raise ValueError("expert_dtype needs an MoE model: a dense model "
+                             "has no experts")
+        if self.expert_dtype not in ("bf16", allowed):
+            raise ValueError(f"experts are already {self.expert_dtype}, "
+                             f"cannot convert them to {expert_dtype}")
+        if self.device.type == "cuda" and self.dtype != torch.bfloat16:
+            raise ValueError(f"{expert_dtype} experts on the GPU need a bf16 "
+                             "runner")
+        if expert_dtype == "mxfp4" and (c.hidden_size % 32 or
+                                        c.moe_intermediate_size % 32):
+            raise ValueError(
+                "mxfp4 experts need hidden_size and moe_intermediate_size to "
+                f"be multiples of 32, got {c.hidden_size} and "
+                f"{c.moe_intermediate_size}")
+
+    def quantize_experts(self, expert_dtype: str) -> None:
+        """Convert w13 and w2 of every layer in place, expert by expert, each
+        bf16 tensor dropped as it is converted. "fp8": the pairs (w13q
+        [E, 2 I, H] float8_e4m3fn, w13s [E, 2 I] fp32) and (w2q [E, H, I],
+        w2s [E, H]) of ops.ref.quantize_experts_fp8, legal for every MoE
+        config. "mxfp4": (w13q [E, 2 I, H / 2], w13s [E, 2 I, H / 32]) and
+        (w2q [E, H, I / 2], w2s [E, H, I / 32]), all uint8;
+        hidden_size and moe_intermediate_size must be multiples of 32, the
+        MX group. wqkv, wo, the router, the embedding, lm_head and the norms
+        are left alone. Experts that are already quantised cannot be
+        converted again: the bf16 weights are gone."""
+        self._check_expert_dtype(expert_dtype, "bf16")
+        quantize = ops_ref.quantize_experts_fp8 if expert_dtype == "fp8" \
+            else ops_ref.quantize_experts_mxfp4
+        for layer in self.layers:
+            for name in ("w13", "w2"):
+                layer[name] = quantize(layer[name])
+        self.expert_dtype = expert_dtype
 
     def dense_layers(self) -> List[Dict[str, torch.Tensor]]:
         """self.layers with the four projections as fp32 [in, out] tensors,
         an fp8 or mxfp4 pair dequantised exactly: the weights the forward
-        pass applies. MXFP4 experts come back as fp32 [E, out, in]."""
+        pass applies. MXFP4 and fp8 experts come back as fp32 [E, out, in]."""
         def dense(w):
             if not isinstance(w, tuple):
                 return w.float()
@@ -237,8 +278,11 @@ class LlamaRunner:
                 return ops_ref.dequant_mxfp4_weight(*w, dtype=torch.float32)
             return (w[0].float() * w[1][:, None]).t()
         def experts(w):
+            if not isinstance(w, tuple):
+                return w
             return ops_ref.dequant_experts_mxfp4(*w) \
-                if isinstance(w, tuple) else w
+                if w[0].dtype == torch.uint8 else \
+                ops_ref.dequant_experts_fp8(*w)
         return [{k: dense(w) if k in LORA_TARGETS else
                  experts(w) if k in ("w13", "w2") else w
                  for k, w in layer.items()} for layer in self.layers]
@@ -281,11 +325,14 @@ class LlamaRunner:
         c = self.cfg
         ids, w = ops.moe_route(x, layer["router"], c.experts_per_token,
                                c.norm_topk_prob)
-        mx = isinstance(layer["w13"], tuple)     # MXFP4 pairs
-        if mx:
-            ffn, experts = ops.moe_ffn_mxfp4, (*layer["w13"], *layer["w2"])
-        else:
+        # a bf16 tensor, an MXFP4 pair (uint8) or an fp8 pair
+        mx = False
+        if not isinstance(layer["w13"], tuple):
             ffn, experts = ops.moe_ffn, (layer["w13"], layer["w2"])
+        else:
+            mx = layer["w13"][0].dtype == torch.uint8
+            ffn = ops.moe_ffn_mxfp4 if mx else ops.moe_ffn_fp8
+            experts = (*layer["w13"], *layer["w2"])
         if not x.is_cuda:
             return ffn(x, *experts, ids, w)
         key = torch.cuda.current_stream(x.device).cuda_stream

@@ -1,7 +1,7 @@
 from .dispatch import (  # noqa: F401
     dequant_fp8_weight, dequant_mxfp4_weight, flash_prefill, hip_ops,
-    linear_fp8, linear_mxfp4, lora_add, lora_worklist, moe_ffn, moe_ffn_mxfp4,
-    moe_route,
+    linear_fp8, linear_mxfp4, lora_add, lora_worklist, moe_ffn, moe_ffn_fp8,
+    moe_ffn_mxfp4, moe_route,
     moe_scratch_bytes, move_blocks,
     paged_attention, qkv_rope_cache,
     reshape_and_cache, rmsnorm, rope, sample, sample_ext, silu_mul,

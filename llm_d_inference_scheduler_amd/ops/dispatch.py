@@ -325,6 +325,21 @@ def moe_ffn_mxfp4(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
     return ref.moe_ffn_mxfp4(x, w13q, w13s, w2q, w2s, ids, w)
 
 
+def moe_ffn_fp8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
+                w2q: torch.Tensor, w2s: torch.Tensor, ids: torch.Tensor,
+                w: torch.Tensor,
+                scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_ffn on fp8 experts (DEVELOPMENT.md "Mixture of experts"): w13q
+    [E, 2 I, H] and w2q [E, H, I] float8_e4m3fn, w13s [E, 2 I] and w2s [E, H]
+    fp32, the pair of ops.ref.quantize_weight_fp8 per expert. The scales
+    multiply the fp32 sums: gate and up before silu(g) * u, down before the
+    routing weight. H % 32 == 0 and I % 16 == 0. scratch (GPU only): at least
+    moe_scratch_bytes, as for moe_ffn."""
+    if _use_hip(x):
+        return _ext.moe_ffn_fp8(x, w13q, w13s, w2q, w2s, ids, w, scratch)
+    return ref.moe_ffn_fp8(x, w13q, w13s, w2q, w2s, ids, w)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

@@ -865,6 +865,31 @@ def moe_ffn_mxfp4(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
                    dequant_experts_mxfp4(w2q, w2s), ids, w)
 
 
+def quantize_experts_fp8(W: torch.Tensor):
+    """W [E, out, in] -> (wq [E, out, in] float8_e4m3fn, scale [E, out]
+    fp32): quantize_weight_fp8 expert by expert, so the peak is one expert's
+    fp32 copy."""
+    pairs = [quantize_weight_fp8(W[e].t()) for e in range(W.shape[0])]
+    return (torch.stack([p[0] for p in pairs]),
+            torch.stack([p[1] for p in pairs]))
+
+
+def dequant_experts_fp8(wq: torch.Tensor, scale: torch.Tensor,
+                        dtype=torch.float32) -> torch.Tensor:
+    """[E, out, in] in `dtype`: float(wq) * scale[e, n] in fp32. Not a bf16
+    in general: the kernels multiply the fp32 sums by the scale instead."""
+    return (wq.float() * scale[..., None]).to(dtype)
+
+
+def moe_ffn_fp8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
+                w2q: torch.Tensor, w2s: torch.Tensor, ids: torch.Tensor,
+                w: torch.Tensor) -> torch.Tensor:
+    """moe_ffn on the dequantised experts of fp8 pairs w13q [E, 2 I, H],
+    w13s [E, 2 I], w2q [E, H, I], w2s [E, H]."""
+    return moe_ffn(x, dequant_experts_fp8(w13q, w13s),
+                   dequant_experts_fp8(w2q, w2s), ids, w)
+
+
 _PREFIX_MODEL = PrefixModel()
 hash_prompts = _PREFIX_MODEL.hash_prompts
 table_update = _PREFIX_MODEL.table_update

@@ -42,7 +42,15 @@ def parse_args(argv=None):
                         "per output channel (half the weight bytes); mxfp4: "
                         "OCP Microscaling FP4 projections, e2m1 with one "
                         "e8m0 exponent per 32 values (17/64 of the bytes); "
-                        "an MoE model takes mxfp4 only, experts included")
+                        "an MoE model takes mxfp4 only, experts included, "
+                        "unless --expert-dtype is given")
+    p.add_argument("--expert-dtype", default="auto",
+                   choices=["auto", "bf16", "fp8", "mxfp4"],
+                   help="MoE models: the format of the experts, with "
+                        "--weight-dtype then governing wqkv and wo alone "
+                        "(fp8: e4m3 with one scale per expert and output "
+                        "channel; mxfp4 as above); auto: the experts follow "
+                        "--weight-dtype")
     p.add_argument("--kv-scales", default=None,
                    help='per-head scales of an fp8 KV cache: "none", '
                         '"calibrate" (synthetic tokens at start-up) or the '
@@ -109,7 +117,7 @@ def build_node(args):
         kv_blocks=None if use_gpu else 2048,
         kv_budget_bytes=int(args.kv_gb * (1 << 30)),
         kv_cache_dtype=args.kv_dtype, weight_dtype=args.weight_dtype,
-        flow_control=args.flow_control,
+        expert_dtype=args.expert_dtype, flow_control=args.flow_control,
         decode_chunk_tokens=args.decode_chunk_tokens or None,
         seed=args.seed, max_loras=args.max_loras,
         max_lora_rank=args.max_lora_rank,

@@ -1,7 +1,8 @@
 """Microbench of the MoE layer (ops.moe_route + ops.moe_ffn) at
 Qwen3-30B-A3B shapes (results: profiles/moe.md).
 
-    python tools/moe_bench.py [--rounds 7] [--copies 8] [--weights mxfp4]
+    python tools/moe_bench.py [--rounds 7] [--copies 8]
+                              [--weights mxfp4|fp8]
 
 One layer: H 2048, 128 experts of I 768, 8 a token, for T in {1, 16, 64, 256,
 1024, 4096}. Arms, timed in one process in interleaved rounds (arm order
@@ -33,6 +34,16 @@ experts with ops.ref.quantize_weight_mxfp4 and times two arms instead:
 `floor` is then that of the mxfp4 arm, 4.25 bits a weight (codes and scale
 bytes), and `floor_bf16` the bf16 arm's. The mxfp4 output is checked against
 the float64 bound on the dequantised experts before each T is timed.
+
+--weights fp8 (results: profiles/moe_fp8.md) does the same with
+ops.ref.quantize_experts_fp8:
+  fp8      ops.moe_route, then ops.moe_ffn_fp8 on the fp8 pairs
+  bf16     ops.moe_route, then ops.moe_ffn on the dequantised experts rounded
+           to bf16 (an fp8 weight times its scale is not a bf16, so this arm
+           computes a neighbouring function, at the same cost)
+`floor` is 1 byte a weight plus the fp32 scales of the touched experts. The
+fp8 output is checked against the float64 bound on the float64 experts
+wq * scale before each T is timed, the bf16 arm on its own bf16 experts.
 """
 import argparse
 import json
@@ -121,7 +132,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--copies", type=int, default=8)
-    ap.add_argument("--weights", choices=["bf16", "mxfp4"], default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "mxfp4", "fp8"], default="bf16")
     args = ap.parse_args()
     ops.hip_ops()
     c = QWEN3_30B_A3B
@@ -134,8 +145,8 @@ def main():
     w13s = [randn(E, 2 * I, H).mul_(0.02).bfloat16() for _ in range(n)]
     w2s = [randn(E, H, I).mul_(0.02).bfloat16() for _ in range(n)]
     expert_bytes = 3 * I * H * 2
-    if args.weights == "mxfp4":
-        return main_mxfp4(args, routers, w13s, w2s, randn)
+    if args.weights != "bf16":
+        return main_quantised(args, routers, w13s, w2s, randn)
     for T in TS:
         xs = [randn(T, H).bfloat16() for _ in range(n)]
         scratch = torch.empty(ops.moe_scratch_bytes(T, k, E, H, I),
@@ -169,47 +180,62 @@ def main():
         del xs, scratch
 
 
-def main_mxfp4(args, routers, w13s, w2s, randn):
+def main_quantised(args, routers, w13s, w2s, randn):
+    """--weights mxfp4 / fp8: the quantised arm against the bf16 kernels on a
+    bf16 copy of the same experts."""
+    fmt = args.weights
     n, (E, _, H), I = args.copies, w13s[0].shape, w2s[0].shape[2]
     k = QWEN3_30B_A3B.experts_per_token
     ref = ops.ref
+    quantize, dequant, ffn_q, bits = {
+        "mxfp4": (ref.quantize_experts_mxfp4, ref.dequant_experts_mxfp4,
+                  ops.moe_ffn_mxfp4, 4.25),
+        "fp8": (ref.quantize_experts_fp8, ref.dequant_experts_fp8,
+                ops.moe_ffn_fp8, 8.0)}[fmt]
     q13s, q2s = [], []
     for i in range(n):      # each bf16 copy becomes its own dequantisation
-        q13s.append(ref.quantize_experts_mxfp4(w13s[i]))
-        q2s.append(ref.quantize_experts_mxfp4(w2s[i]))
-        w13s[i] = ref.dequant_experts_mxfp4(*q13s[i], dtype=torch.bfloat16)
-        w2s[i] = ref.dequant_experts_mxfp4(*q2s[i], dtype=torch.bfloat16)
+        q13s.append(quantize(w13s[i]))
+        q2s.append(quantize(w2s[i]))
+        w13s[i] = dequant(*q13s[i], dtype=torch.bfloat16)
+        w2s[i] = dequant(*q2s[i], dtype=torch.bfloat16)
+    # what the quantised arm is judged on: for mxfp4 the bf16 copy is exact;
+    # an fp8 weight times its scale is not a bf16, so float64 holds it
+    exact = (w13s[0], w2s[0]) if fmt == "mxfp4" else tuple(
+        wq.double() * sc.double()[..., None] for wq, sc in (q13s[0], q2s[0]))
     weights = 3 * I * H
+    scale_bytes = 0 if fmt == "mxfp4" else (2 * I + H) * 4   # per expert
+    mx = fmt == "mxfp4"
     for T in TS:
         xs = [randn(T, H).bfloat16() for _ in range(n)]
-        scratch = {mx: torch.empty(
-            ops.moe_scratch_bytes(T, k, E, H, I, mxfp4=mx),
-            dtype=torch.uint8, device=DEV) for mx in (True, False)}
+        scratch = {q: torch.empty(
+            ops.moe_scratch_bytes(T, k, E, H, I, mxfp4=q and mx),
+            dtype=torch.uint8, device=DEV) for q in (True, False)}
 
-        def mxfp4(i):
+        def quantised(i):
             ids, w = ops.moe_route(xs[i], routers[i], k, True)
-            return ops.moe_ffn_mxfp4(xs[i], *q13s[i], *q2s[i], ids, w,
-                                     scratch[True])
+            return ffn_q(xs[i], *q13s[i], *q2s[i], ids, w, scratch[True])
 
         def bf16(i):
             ids, w = ops.moe_route(xs[i], routers[i], k, True)
             return ops.moe_ffn(xs[i], w13s[i], w2s[i], ids, w, scratch[False])
 
         ids, w = ops.moe_route(xs[0], routers[0], k, True)
-        for what, y in (("mxfp4", mxfp4(0)), ("bf16", bf16(0))):
-            excess = moe_cases.ffn_excess(y, xs[0], w13s[0], w2s[0], ids, w)
+        for what, y, (e13, e2) in ((fmt, quantised(0), exact),
+                                   ("bf16", bf16(0), (w13s[0], w2s[0]))):
+            excess = moe_cases.ffn_excess(y, xs[0], e13, e2, ids, w)
             if excess > 0:
                 raise SystemExit(f"T={T} {what}: excess {excess:.3e}")
             print(f"# T={T} {what} excess {excess:.3e}", flush=True)
         touched = statistics.mean(
             int(torch_route(xs[i], routers[i], k)[0].unique().numel())
             for i in range(n))
-        fns = {"mxfp4": rotating(mxfp4, n), "bf16": rotating(bf16, n)}
-        floor = lambda bits: round(
-            (touched * weights * bits / 8 + E * H * 2) / HBM_BYTES_PER_US, 2)
+        fns = {fmt: rotating(quantised, n), "bf16": rotating(bf16, n)}
+        floor = lambda bits, extra: round(
+            (touched * (weights * bits / 8 + extra) + E * H * 2)
+            / HBM_BYTES_PER_US, 2)
         print(json.dumps(dict(
             T=T, H=H, I=I, E=E, k=k, copies=n, experts=round(touched, 1),
-            floor=floor(4.25), floor_bf16=floor(16),
+            floor=floor(bits, scale_bytes), floor_bf16=floor(16, 0),
             **bench(fns, args.rounds))), flush=True)
         del xs, scratch
 
