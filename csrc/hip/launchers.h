@@ -190,6 +190,43 @@ hipError_t lds_linear_fp8(const LinearFp8Args& a, hipStream_t stream);
 hipError_t lds_dequant_fp8_weight(const void* wq, const float* scale, void* W,
                                   int in, int out, hipStream_t stream);
 
+// ---- linear_fp8_a8.hip ---------------------------------------------------
+
+// bytes of K a workgroup stages per step: one 16x16x128 fp8 MFMA deep
+constexpr int LINEAR_FP8_A8_BK = 128;
+// The 128 x 128 tile reads half the LDS bytes per MFMA of the 64 x 64 one,
+// but only pays once its grid gives every CU a workgroup (256 CUs); below
+// that the small tile spreads the same work over four times the CUs.
+constexpr int LINEAR_FP8_A8_FILL_WGS = 256;
+
+// Output tile edge of the fp8-activation GEMM (64 and 128 are
+// instantiated). The tile decides who computes an element, never the order
+// of its sum.
+inline int linear_fp8_a8_tile(int T, int out) {
+  const int64_t wgs = (int64_t)((T + 127) / 128) * ((out + 127) / 128);
+  return wgs >= LINEAR_FP8_A8_FILL_WGS ? 128 : 64;
+}
+
+// xq[m, k] = e4m3(clamp(x[m, k] / sx[m], +-448)), sx[m] = absmax(x[m, :]) /
+// 448 (1 for a zero row): x [T, in] bf16, in % 64 == 0, x and xq 16-byte
+// aligned.
+hipError_t lds_quantize_rows_fp8(const void* x, void* xq, float* sx, int T,
+                                 int in, hipStream_t stream);
+
+// y[m, n] = bf16(sx[m] * scale[n] * sum_k float(xq[m, k]) * float(wq[n, k])),
+// fp32 sums on the fp8 MFMA.
+struct LinearFp8A8Args {
+  const void* xq;       // [T, in] OCP e4m3, in % 64 == 0, 16-byte aligned
+  const float* sx;      // [T]
+  const void* wq;       // [out, in] OCP e4m3, out % 16 == 0, 16-byte aligned
+  const float* scale;   // [out]
+  void* y;              // [T, out] bf16, 16-byte aligned
+  int T, in, out;
+  int tile;             // linear_fp8_a8_tile(T, out); 64 or 128
+};
+
+hipError_t lds_linear_fp8_a8(const LinearFp8A8Args& a, hipStream_t stream);
+
 // ---- linear_mxfp4.hip ----------------------------------------------------
 
 // k a wave consumes per step: one 32-wide MX group a lane group, four MFMAs.

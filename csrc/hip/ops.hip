@@ -696,6 +696,60 @@ void dequant_fp8_weight(torch::Tensor wq, torch::Tensor scale,
                                    out.data_ptr(), in, n_out, cur_stream()));
 }
 
+// ---- fp8 activations ----
+
+// The rows an fp8-activation op takes: x [T, in] bf16, in a multiple of 64,
+// 16-byte aligned. Returns (T, in).
+std::pair<int, int> check_fp8_rows(const torch::Tensor& x) {
+  check_tensor(x, "x", x, "x", at::kBFloat16, {ANY, ANY});
+  TORCH_CHECK(x.size(1) % LINEAR_FP8_KBLOCK == 0, "x.size(1) must be a "
+              "multiple of ", LINEAR_FP8_KBLOCK, ", got ", x.size(1));
+  check_aligned16(x, "x");
+  return {check_int(x.size(0), 0, GRID_YZ_MAX * 64, "x.size(0)"),
+          check_int(x.size(1), 0, INT_MAX, "x.size(1)")};
+}
+
+// (xq [T, in] e4m3, sx [T] fp32): the per-row dynamic quantisation of x,
+// the bytes of ops.ref.quantize_rows_fp8.
+std::tuple<torch::Tensor, torch::Tensor> quantize_rows_fp8(torch::Tensor x) {
+  const auto [T, in] = check_fp8_rows(x);
+  auto xq = torch::empty({T, in}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto sx = torch::empty({T}, x.options().dtype(torch::kFloat32));
+  CHECK_HIP(lds_quantize_rows_fp8(x.data_ptr(), xq.data_ptr(),
+                                  sx.data_ptr<float>(), T, in, cur_stream()));
+  return {xq, sx};
+}
+
+// y = bf16(sx * scale * (xq · wqᵀ)) with fp32 sums on the fp8 MFMA: x
+// [T, in] bf16, quantised per row here, against an fp8 weight. tile is the
+// launch geometry, for measurement and tests only: 0 is what serves
+// (linear_fp8_a8_tile) and what ops.linear_fp8_a8 always passes. The tile
+// never changes a bit of y.
+torch::Tensor linear_fp8_a8(torch::Tensor x, torch::Tensor wq,
+                            torch::Tensor scale, int64_t tile) {
+  const auto [T, in] = check_fp8_rows(x);
+  check_fp8_weight(wq, scale, x, "x");
+  TORCH_CHECK(x.size(1) == wq.size(1), "x.size(1) (", x.size(1), ") must be "
+              "wq.size(1) (", wq.size(1), ")");
+  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128, "tile must be 0, 64 "
+              "or 128, got ", tile);
+  LinearFp8A8Args a{};
+  a.T = T;
+  a.in = in;
+  a.out = check_int(wq.size(0), 0, INT_MAX, "wq.size(0)");
+  a.tile = tile ? (int)tile : linear_fp8_a8_tile(a.T, a.out);
+  auto y = torch::empty({a.T, a.out}, x.options());
+  if (a.T == 0 || a.out == 0) return y;
+  auto [xq, sx] = quantize_rows_fp8(x);
+  a.xq = xq.data_ptr();
+  a.sx = sx.data_ptr<float>();
+  a.wq = wq.data_ptr();
+  a.scale = scale.data_ptr<float>();
+  a.y = y.data_ptr();
+  CHECK_HIP(lds_linear_fp8_a8(a, cur_stream()));
+  return y;
+}
+
 // ---- mxfp4 weights ----
 
 // The (wq, scale) pair of an MXFP4 weight (DEVELOPMENT.md "MXFP4 weights"),
@@ -1236,6 +1290,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequant_fp8_weight", &dequant_fp8_weight,
         "expand an fp8 weight into out [in, out] bf16",
         py::arg("wq"), py::arg("scale"), py::arg("out"));
+  m.def("quantize_rows_fp8", &quantize_rows_fp8,
+        "x [T, in] bf16 -> (xq [T, in] e4m3, sx [T] fp32), one dynamic "
+        "scale per row",
+        py::arg("x"));
+  m.def("linear_fp8_a8", &linear_fp8_a8,
+        "x [T, in] bf16, quantised per row to fp8, against an fp8 weight "
+        "(wq [out, in] e4m3, scale [out] fp32) on the fp8 MFMA -> y "
+        "[T, out] bf16; tile: measurement knob, never changes y",
+        py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("tile") = 0);
   m.def("linear_mxfp4", &linear_mxfp4,
         "x [T, in] bf16 against an MXFP4 weight (wq [out, in / 2] uint8, "
         "scale [out, in / 32] uint8 e8m0) -> y [T, out] bf16; bn, k_splits: "

@@ -411,7 +411,8 @@ class EngineWorker:
                  max_loras: int = 0,
                  max_lora_rank: int = 16,
                  weight_dtype: str = "auto",
-                 expert_dtype: str = "auto"):
+                 expert_dtype: str = "auto",
+                 activation_dtype: str = "auto"):
         """weight_dtype "fp8" stores the four projections of every layer as
         weight-only fp8 with one scale per output channel (DEVELOPMENT.md
         "fp8 weights"), "mxfp4" as OCP Microscaling FP4, e2m1 codes with one
@@ -427,6 +428,15 @@ class EngineWorker:
         all-fp8 MoE model, "mxfp4" with weight_dtype "auto" MXFP4 experts
         under bf16 attention. "auto" is the rule above, under which
         weight_dtype "fp8" alone on an MoE model is an error.
+
+        activation_dtype "fp8" (with weight_dtype "fp8" only; anything else
+        is a ValueError) runs batches above the weight-only kernel's
+        crossover with fp8 activations, quantised per token with a dynamic
+        scale, on the fp8 MFMA (DEVELOPMENT.md "fp8 activations"). The
+        quantisation a row sees then depends on the size of the batch it
+        ran in. On an MoE model it covers wqkv and wo; the experts are
+        untouched. "auto" and "bf16" keep bf16 activations. Both ranks of a
+        P/D pair must use the same value.
 
         kv_scales selects the per-head scales of an fp8 KV cache
         (KVPool): "none" (unscaled direct cast), "calibrate" (run
@@ -447,6 +457,11 @@ class EngineWorker:
                              "model (max_loras must be 0)")
         if expert_dtype not in ("auto", "bf16", "fp8", "mxfp4"):
             raise ValueError(f"unknown expert_dtype {expert_dtype!r}")
+        if activation_dtype not in ("auto", "bf16", "fp8"):
+            raise ValueError(f"unknown activation_dtype {activation_dtype!r}")
+        if activation_dtype == "fp8" and weight_dtype != "fp8":
+            raise ValueError('activation_dtype "fp8" needs weight_dtype '
+                             f'"fp8", got weight_dtype {weight_dtype!r}')
         if expert_dtype != "auto" and not config.num_experts:
             raise ValueError(f"expert_dtype {expert_dtype!r} needs an MoE "
                              "model: a dense model has no experts")
@@ -482,6 +497,7 @@ class EngineWorker:
             self.model.quantize_weights(weight_dtype, experts=False)
             if expert_dtype != "bf16":
                 self.model.quantize_experts(expert_dtype)
+        self.model.set_activation_dtype(activation_dtype)
         self.seed = seed
         self.max_loras = max_loras
         self.adapters: Dict[str, LoraAdapter] = {}   # registered, on the host

@@ -166,6 +166,10 @@ class LlamaRunner:
         self.expert_dtype = "bf16"     # w13 and w2 (quantize_experts)
         self._fp8_kernel_max_t = 128
         self._mxfp4_kernel_max_t = 128
+        # "fp8" (set_activation_dtype): fp8 pairs at batches above
+        # _fp8_kernel_max_t go through ops.linear_fp8_a8 instead, and the
+        # bf16 scratch below is never allocated
+        self.activation_dtype = "bf16"
         self._fp8_scratch: Dict[int, torch.Tensor] = {}
         # ops.moe_ffn / moe_ffn_mxfp4 / moe_ffn_fp8 scratch, one per stream, sized by
         # the largest T seen
@@ -224,6 +228,25 @@ class LlamaRunner:
         self.weight_dtype = weight_dtype
         if experts:
             self.quantize_experts(weight_dtype)
+
+    def set_activation_dtype(self, activation_dtype: str) -> None:
+        """With "fp8" (DEVELOPMENT.md "fp8 activations") batches of more than
+        _fp8_kernel_max_t rows are quantised per row to e4m3 with a dynamic
+        scale and multiplied by the fp8 weights on the fp8 MFMA
+        (ops.linear_fp8_a8) instead of going through a dequantised bf16 copy
+        and torch.matmul. Needs quantize_weights("fp8") first. Smaller
+        batches keep the weight-only kernel, so the quantisation a row sees
+        depends on the size of the batch it ran in. The experts of an MoE
+        model are untouched. "auto" and "bf16" change nothing."""
+        if activation_dtype not in ("auto", "bf16", "fp8"):
+            raise ValueError(f"unknown activation_dtype {activation_dtype!r}")
+        if activation_dtype != "fp8":
+            return
+        if self.weight_dtype != "fp8":
+            raise ValueError(
+                'activation_dtype "fp8" needs weight_dtype "fp8", the '
+                f"weights are {self.weight_dtype}")
+        self.activation_dtype = "fp8"
 
     def _check_expert_dtype(self, expert_dtype: str, allowed: str) -> None:
         """ValueError unless the experts can become expert_dtype: an MoE model
@@ -353,6 +376,8 @@ class LlamaRunner:
         wq, scale = w
         mx = wq.dtype == torch.uint8
         max_t = self._mxfp4_kernel_max_t if mx else self._fp8_kernel_max_t
+        if not mx and self.activation_dtype == "fp8" and x.shape[0] > max_t:
+            return ops.linear_fp8_a8(x, wq, scale)
         if not x.is_cuda or x.shape[0] <= max_t:
             return ops.linear_mxfp4(x, wq, scale) if mx else \
                 ops.linear_fp8(x, wq, scale)

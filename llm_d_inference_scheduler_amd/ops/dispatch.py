@@ -254,6 +254,28 @@ def dequant_fp8_weight(wq: torch.Tensor, scale: torch.Tensor,
     return ref.dequant_fp8_weight(wq, scale, out)
 
 
+def quantize_rows_fp8(x: torch.Tensor):
+    """x [T, in] bf16 -> (xq [T, in] float8_e4m3fn, sx [T] fp32), the dynamic
+    per-row quantisation of DEVELOPMENT.md "fp8 activations": sx[m] =
+    absmax(x[m, :]) / 448 (1 for a zero row), xq = x / sx rounded to e4m3.
+    The bytes of ops.ref.quantize_rows_fp8 on either device. in % 64 == 0."""
+    if _use_hip(x):
+        return _ext.quantize_rows_fp8(x)
+    return ref.quantize_rows_fp8(x)
+
+
+def linear_fp8_a8(x: torch.Tensor, wq: torch.Tensor,
+                  scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in] bf16 against an fp8 weight with fp8 activations
+    (DEVELOPMENT.md "fp8 activations"): x is quantised per row by
+    quantize_rows_fp8 and multiplied by wq [out, in] float8_e4m3fn on the
+    fp8 MFMA -> y [T, out], y[m, n] = sx[m] * scale[n] * sum_k float(xq[m, k])
+    * float(wq[n, k]) with fp32 sums. in % 64 == 0, out % 16 == 0."""
+    if _use_hip(x):
+        return _ext.linear_fp8_a8(x, wq, scale)
+    return ref.linear_fp8_a8(x, wq, scale)
+
+
 def linear_mxfp4(x: torch.Tensor, wq: torch.Tensor,
                  scale: torch.Tensor) -> torch.Tensor:
     """x [T, in] bf16 against an MXFP4 weight (DEVELOPMENT.md "MXFP4

@@ -728,6 +728,31 @@ def linear_fp8(x: torch.Tensor, wq: torch.Tensor,
     return (x.float() @ (wq.float() * scale[:, None]).t()).to(x.dtype)
 
 
+# ---- fp8 activations (DEVELOPMENT.md "fp8 activations") --------------------
+
+def quantize_rows_fp8(x: torch.Tensor):
+    """x [T, K] -> (xq [T, K] float8_e4m3fn, sx [T] fp32), one dynamic scale
+    per row: sx[m] = absmax(x[m, :]) / 448 (1 for an all-zero row) and
+    xq[m, k] = x[m, k] / sx[m] rounded to e4m3. quantize_weight_fp8 per row
+    instead of per column: fp32 division and round-to-nearest-even, so a
+    CPU and a GPU worker hold the same bytes."""
+    xf = x.detach().float()
+    amax = xf.abs().amax(dim=1)
+    sx = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    xq = (xf / sx[:, None]).clamp_(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return xq.to(torch.float8_e4m3fn).contiguous(), sx.contiguous()
+
+
+def linear_fp8_a8(x: torch.Tensor, wq: torch.Tensor,
+                  scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in], quantised per row by quantize_rows_fp8, against an fp8
+    weight -> [T, out] in x's dtype: y[m, n] = sx[m] * scale[n] * sum_k
+    float(xq[m, k]) * float(wq[n, k]), fp32 sums, sx applied first."""
+    xq, sx = quantize_rows_fp8(x)
+    acc = xq.float() @ wq.float().t()
+    return (acc * sx[:, None] * scale[None, :]).to(x.dtype)
+
+
 # ---- MXFP4 weights (DEVELOPMENT.md "MXFP4 weights") -----------------------
 
 MXFP4_GROUP = 32

@@ -51,6 +51,13 @@ def parse_args(argv=None):
                         "(fp8: e4m3 with one scale per expert and output "
                         "channel; mxfp4 as above); auto: the experts follow "
                         "--weight-dtype")
+    p.add_argument("--activation-dtype", default="auto",
+                   choices=["auto", "bf16", "fp8"],
+                   help="fp8 (needs --weight-dtype fp8): batches above the "
+                        "weight-only kernel's crossover run with per-token "
+                        "dynamic e4m3 activations on the fp8 MFMA; the "
+                        "quantisation a row sees then depends on the size "
+                        "of its batch")
     p.add_argument("--kv-scales", default=None,
                    help='per-head scales of an fp8 KV cache: "none", '
                         '"calibrate" (synthetic tokens at start-up) or the '
@@ -117,7 +124,9 @@ def build_node(args):
         kv_blocks=None if use_gpu else 2048,
         kv_budget_bytes=int(args.kv_gb * (1 << 30)),
         kv_cache_dtype=args.kv_dtype, weight_dtype=args.weight_dtype,
-        expert_dtype=args.expert_dtype, flow_control=args.flow_control,
+        expert_dtype=args.expert_dtype,
+        activation_dtype=args.activation_dtype,
+        flow_control=args.flow_control,
         decode_chunk_tokens=args.decode_chunk_tokens or None,
         seed=args.seed, max_loras=args.max_loras,
         max_lora_rank=args.max_lora_rank,

@@ -1,7 +1,7 @@
 """Microbench of the fp8-weights linear against the bf16 GEMM it replaces
 (results: profiles/linear_fp8.md).
 
-    python tools/linear_fp8_bench.py [--format fp8|mxfp4] [--rounds 9]
+    python tools/linear_fp8_bench.py [--format fp8|mxfp4|fp8a8] [--rounds 9]
                                      [--geometry]
 
 Shapes: the four projections of Llama-3-8B and of Qwen3-32B, for T in
@@ -30,6 +30,12 @@ ops.dequant_mxfp4_weight + matmul as `kernel` and `dequant` instead, for T in
 {1, 4, 16, 32, 64, 128, 256}, keeps the fp8 kernel as the arm `fp8` in the
 same rounds, and adds `<arm>_spread`, the largest minus the smallest round of
 an arm; `floor` then counts the codes and the scale bytes.
+--format fp8a8 (results: profiles/linear_fp8_a8.md) is the prefill side, T in
+{128, 256, 512, 1024, 2048, 4096}: `a8` is ops.linear_fp8_a8 as the runner
+calls it (per-row quantiser + fp8 MFMA GEMM), `quant` the quantiser alone
+(its share of `a8`), `dequant` and `bf16` as above, with `<arm>_spread`. `a8`
+is first compared with the float64 product of the dequantised codes under
+the bound of tests/test_gpu_linear_fp8_a8.py.
 """
 import argparse
 import json
@@ -50,6 +56,8 @@ from llm_d_inference_scheduler_amd.models.llama import (  # noqa: E402
 DEV = "cuda"
 TS = (1, 8, 16, 32, 64, 128, 256)
 TS_MXFP4 = (1, 4, 16, 32, 64, 128, 256)
+TS_A8 = (128, 256, 512, 1024, 2048, 4096)
+A8_MFMA_COEFF = 2 * 1718    # tests/test_gpu_linear_fp8_a8.py MFMA_COEFF
 WINDOW_US = 10000.0
 COLD_BYTES = 512 << 20
 HBM_BYTES_PER_US = 8e6
@@ -119,15 +127,34 @@ def check(y, x, wq, scale, what, mx=False):
         raise SystemExit(f"{what}: {int(bad.sum())} elements out of bound")
 
 
+def check_a8(y, x, wq, scale):
+    """ops.linear_fp8_a8's y against float64 on the dequantised codes, first
+    8 rows, under the bound of tests/test_gpu_linear_fp8_a8.py."""
+    n = min(8, x.shape[0])
+    xq, sx = ops.quantize_rows_fp8(x[:n].contiguous())
+    x64 = xq.double() * sx.double()[:, None]
+    w64 = (wq.double() * scale.double()[:, None]).t()
+    y64 = x64 @ w64
+    coeff = max(x.shape[1], A8_MFMA_COEFF) * 2.0 ** -23
+    bad = (y[:n].double() - y64).abs() > \
+        2.0 ** -8 * y64.abs() + coeff * (x64.abs() @ w64.abs())
+    if bool(bad.any()):
+        raise SystemExit(f"a8: {int(bad.sum())} elements out of bound")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--format", choices=["fp8", "mxfp4"], default="fp8")
+    ap.add_argument("--format", choices=["fp8", "mxfp4", "fp8a8"],
+                    default="fp8")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--geometry", action="store_true")
     ap.add_argument("--warm", action="store_true")
     args = ap.parse_args()
     ext = ops.hip_ops()
     mx = args.format == "mxfp4"
+    a8 = args.format == "fp8a8"
+    if a8 and args.geometry:
+        raise SystemExit("--geometry is not defined for --format fp8a8")
     linear, dequant = (ops.linear_mxfp4, ops.dequant_mxfp4_weight) if mx \
         else (ops.linear_fp8, ops.dequant_fp8_weight)
     ext_linear = ext.linear_mxfp4 if mx else ext.linear_fp8
@@ -150,7 +177,7 @@ def main():
                 -(-COLD_BYTES // (2 * W.numel()))
             wqs = [wq] + [wq.clone() for _ in range(n8 - 1)]
             Ws = [W] + [W.clone() for _ in range(n16 - 1)]
-            for T in TS_MXFP4 if mx else TS:
+            for T in TS_A8 if a8 else TS_MXFP4 if mx else TS:
                 if args.geometry and T not in (1, 16, 32, 64):
                     continue
                 x = torch.randn(T, n_in, generator=gen).to(torch.bfloat16) \
@@ -163,6 +190,17 @@ def main():
                         lambda i, bn=bn, s=s: ext_linear(
                             x, wqs[i], scale, bn, s), n8)
                         for bn, s in geometries}
+                elif a8:
+                    check_a8(ops.linear_fp8_a8(x, wq, scale), x, wq, scale)
+                    check(x @ dequant(wq, scale, dense), x, wq, scale,
+                          "dequant")
+                    fns = {
+                        "a8": rotating(lambda i: ops.linear_fp8_a8(
+                            x, wqs[i], scale), n8),
+                        "quant": lambda: ops.quantize_rows_fp8(x),
+                        "dequant": rotating(
+                            lambda i: x @ dequant(wqs[i], scale, dense), n8),
+                        "bf16": rotating(lambda i: x @ Ws[i], n16)}
                 else:
                     check(linear(x, wq, scale), x, wq, scale, "kernel", mx)
                     check(x @ dequant(wq, scale, dense), x, wq, scale,
@@ -181,7 +219,7 @@ def main():
                     copies=n8, floor=round(
                         (wq.numel() + (scale.numel() if mx else 0))
                         / HBM_BYTES_PER_US, 2),
-                    **bench(fns, args.rounds, spread=mx))), flush=True)
+                    **bench(fns, args.rounds, spread=mx or a8))), flush=True)
             del W, wq, scale, dense, wqs, Ws
             if mx and not args.geometry:
                 del wq8, scale8, wq8s
