@@ -388,6 +388,59 @@ struct MoeFfnFp8Args {
 
 hipError_t lds_moe_ffn_fp8(const MoeFfnFp8Args& a, hipStream_t stream);
 
+// The work list and the slot sum on their own, for moe_fp8_a8.hip: tiles
+// [n, 3] = (start, count <= TM, expert), n_tiles and perm (sorted position ->
+// pair) of the P pairs of ids, with every expert's segment padded to TM rows;
+// y[t] = bf16(sum_j y2[t k + j]) in slot order. T >= 1.
+hipError_t lds_moe_align(const int32_t* ids, int32_t* tiles, int32_t* n_tiles,
+                         int32_t* perm, int64_t P, int E, int TM,
+                         hipStream_t stream);
+hipError_t lds_moe_combine(const float* y2, void* y, int T, int H, int k,
+                           hipStream_t stream);
+
+// ---- moe_fp8_a8.hip ------------------------------------------------------
+
+// Tile height of the fp8-activation expert GEMMs (64 and 128 are
+// instantiated), from the mean rows per expert alone. Every expert's segment
+// is padded to whole tiles, half a tile of dead MFMA rows an expert on
+// average: at a mean of 64 rows or fewer a 128-row tile would be half padding
+// or worse, above it the taller tile reads each weight byte for twice the
+// rows. The threshold is that reasoning about padding, not a sweep. The tile
+// decides who computes an element, never its bits.
+inline int moe_fp8_a8_tile(int64_t P, int E) { return P / E > 64 ? 128 : 64; }
+
+// moe_ffn on fp8 experts with fp8 activations on the fp8 MFMA (W8A8):
+//   (xq, sx) = quantize_rows_fp8(x)
+//   act[p, n] = bf16(silu(g) * u), g = (sum_k xq[t, k] w13q[e, n, k]) * sx[t]
+//               * w13s[e, n], u the same on row I + n; p = t k + j, e = ids[p]
+//   (aq, sa) = quantize_rows_fp8(act), per pair row
+//   y2[p, n] = (sum_k aq[p, k] w2q[e, n, k]) * sa[p] * w2s[e, n] * w[p]
+//   y[t] = bf16(sum_j y2[t k + j])
+struct MoeFfnFp8A8Args {
+  const void* x;        // [T, H] bf16, H % 64 == 0, 16-byte aligned
+  const void* w13q;     // [E, 2 I, H] e4m3, 16-byte aligned, I % 64 == 0
+  const float* w13s;    // [E, 2 I]
+  const void* w2q;      // [E, H, I] e4m3, 16-byte aligned
+  const float* w2s;     // [E, H]
+  const int32_t* ids;   // [T, k]
+  const float* w;       // [T, k]
+  void* y;              // [T, H] bf16
+  // scratch, every pointer 16-byte aligned; P = T k
+  void* xq;             // [T, H] e4m3
+  float* sx;            // [T]
+  void* act;            // [P, I] bf16, by pair: the scratch's, or act_out
+  void* aq;             // [P, I] e4m3, by pair
+  float* sa;            // [P]
+  float* y2;            // [P, H] fp32, by pair
+  int32_t* tiles;       // [moe_tile_bound, 3]
+  int32_t* n_tiles;     // [1]
+  int32_t* perm;        // [moe_tile_bound * tile]
+  int T, H, I, E, k;
+  int tile;             // moe_fp8_a8_tile(T * k, E); 64 or 128
+};
+
+hipError_t lds_moe_ffn_fp8_a8(const MoeFfnFp8A8Args& a, hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

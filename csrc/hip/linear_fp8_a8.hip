@@ -60,6 +60,7 @@
 // which only decides who computes an element.
 #include "hip_common.h"
 #include "launchers.h"
+#include "fp8_tile.h"
 
 // Built without packed fp32 arithmetic (v_pk_add_f32, v_pk_mul_f32,
 // v_pk_fma_f32), as linear_fp8.hip is and for the reason given there: some
@@ -74,15 +75,8 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+using namespace fp8_tile;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-constexpr int A8_THREADS = 256;
-constexpr int A8_WAVES = A8_THREADS / WAVE;
-constexpr int BK = LINEAR_FP8_A8_BK;     // bytes of K a slab
-constexpr int CHUNKS = BK / 16;          // 16-byte chunks of a tile row
-constexpr int E8M0_ONE = 0x7F7F7F7F;     // scale 2^0 in every byte
 
 // ---- quantiser -----------------------------------------------------------
 
@@ -152,72 +146,8 @@ __global__ __launch_bounds__(A8_THREADS) void quantize_rows_fp8_kernel(
 }
 
 // ---- tiled GEMM ----------------------------------------------------------
-
-// the single LDS address function of an operand tile: byte offset of the
-// 16-byte chunk c of row r
-__host__ __device__ constexpr int tile_off(int r, int c) {
-  return r * BK + ((c ^ ((r >> 1) & (CHUNKS - 1))) << 4);
-}
-
-constexpr bool tile_off_conflict_free() {
-  // operand read: 16 consecutive rows at one chunk; staging write: two rows
-  // with all 8 chunks. Both must cover the 16 slots of a 256-byte line.
-  for (int r0 = 0; r0 < 32; r0 += 16)
-    for (int c = 0; c < CHUNKS; ++c) {
-      unsigned seen = 0;
-      for (int r = r0; r < r0 + 16; ++r) seen |= 1u << ((tile_off(r, c) >> 4) & 15);
-      if (seen != 0xFFFFu) return false;
-    }
-  for (int r0 = 0; r0 < 16; r0 += 2) {
-    unsigned seen = 0;
-    for (int q = 0; q < 16; ++q)
-      seen |= 1u << ((tile_off(r0 + (q >> 3), q & 7) >> 4) & 15);
-    if (seen != 0xFFFFu) return false;
-  }
-  return true;
-}
-static_assert(tile_off_conflict_free(), "a pass of 16 lanes covers 16 slots");
-
-// This thread's chunks of one operand's slab: R rows of 32 apart.
-template <int R>
-struct Staging {
-  const unsigned char* src[R];  // global address of the chunk in slab 0
-  int dst[R];                   // tile_off of the chunk
-  u32x4 v[R];
-
-  // rows row0 + (tid >> 3) + 32 i of a [n_rows, in] matrix, clamped
-  __device__ __forceinline__ void init(const unsigned char* base, int row0,
-                                       int n_rows, int in) {
-    const int r = threadIdx.x >> 3, c = threadIdx.x & (CHUNKS - 1);
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      src[i] = base + (int64_t)min(row0 + r + 32 * i, n_rows - 1) * in + c * 16;
-      dst[i] = tile_off(r + 32 * i, c);
-    }
-  }
-  // in_slab: this thread's chunk of the slab lies below `in`
-  __device__ __forceinline__ void load(int slab, bool in_slab) {
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-      v[i] = in_slab ? *(const u32x4*)(src[i] + (int64_t)slab * BK)
-                     : u32x4{0u, 0u, 0u, 0u};
-  }
-  __device__ __forceinline__ void store(unsigned char* tile) const {
-#pragma unroll
-    for (int i = 0; i < R; ++i) *(u32x4*)(tile + dst[i]) = v[i];
-  }
-};
-
-// the 32 operand bytes of this lane for the block whose first row is `row0`
-__device__ __forceinline__ i32x8 read_operand(const unsigned char* tile,
-                                              int row0) {
-  const int lane = threadIdx.x % WAVE;
-  const int r = row0 + (lane & 15), c = (lane >> 4) * 2;
-  union { u32x4 h[2]; i32x8 v; } u;
-  u.h[0] = *(const u32x4*)(tile + tile_off(r, c));
-  u.h[1] = *(const u32x4*)(tile + tile_off(r, c + 1));
-  return u.v;
-}
+// tile_off, Staging, read_operand and the slab loop are in fp8_tile.h, shared
+// with the grouped kernels of moe_fp8_a8.hip.
 
 template <int WM, int WN>
 __global__ __launch_bounds__(A8_THREADS) void linear_fp8_a8_kernel(
@@ -225,7 +155,7 @@ __global__ __launch_bounds__(A8_THREADS) void linear_fp8_a8_kernel(
     const unsigned char* __restrict__ wq, const float* __restrict__ scale,
     short* __restrict__ y, int T, int in, int out) {
   constexpr int BM = 32 * WM, BN = 32 * WN;
-  constexpr int A_BYTES = BM * BK, STAGE = (BM + BN) * BK;
+  constexpr int STAGE = (BM + BN) * BK;
   constexpr int PITCH = BN + 8;  // shorts: rows of the y tile stay 16-byte aligned
   static_assert(BM * PITCH * 2 <= 2 * STAGE, "the y tile fits the slab buffers");
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
@@ -238,48 +168,8 @@ __global__ __launch_bounds__(A8_THREADS) void linear_fp8_a8_kernel(
   Staging<WN> sb;
   sa.init(xq, m0, T, in);
   sb.init(wq, n0, out, in);
-  const int kc = (threadIdx.x & (CHUNKS - 1)) * 16;  // chunk's k in a slab
-
   f32x4 acc[WM][WN];
-#pragma unroll
-  for (int mb = 0; mb < WM; ++mb)
-#pragma unroll
-    for (int nb = 0; nb < WN; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int n_slabs = (in + BK - 1) / BK;
-  sa.load(0, kc < in);
-  sb.load(0, kc < in);
-  sa.store(lds);
-  sb.store(lds + A_BYTES);
-  __syncthreads();
-  for (int s = 0; s < n_slabs; ++s) {
-    const unsigned char* cur = lds + (s & 1) * STAGE;
-    unsigned char* nxt = lds + ((s + 1) & 1) * STAGE;
-    const bool more = s + 1 < n_slabs;
-    if (more) {
-      const bool in_slab = (s + 1) * BK + kc < in;
-      sa.load(s + 1, in_slab);
-      sb.load(s + 1, in_slab);
-    }
-    i32x8 b[WN];
-#pragma unroll
-    for (int nb = 0; nb < WN; ++nb)
-      b[nb] = read_operand(cur + A_BYTES, wn + nb * 16);
-#pragma unroll
-    for (int mb = 0; mb < WM; ++mb) {
-      const i32x8 a = read_operand(cur, wm + mb * 16);
-#pragma unroll
-      for (int nb = 0; nb < WN; ++nb)
-        acc[mb][nb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            a, b[nb], acc[mb][nb], 0, 0, 0, E8M0_ONE, 0, E8M0_ONE);
-    }
-    if (more) {
-      sa.store(nxt);
-      sb.store(nxt + A_BYTES);
-    }
-    // slab s + 1 is visible, and slab s is free for the loads of s + 2
-    __syncthreads();
-  }
+  gemm_slabs<WM, WN>(sa, sb, lds, acc, wm, wn, in);
 
   // D of the MFMA: column n = lane & 15, row m = (lane >> 4) * 4 + j
   short* yt = (short*)lds;

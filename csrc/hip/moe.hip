@@ -1051,6 +1051,25 @@ hipError_t lds_moe_route(const MoeRouteArgs& a, hipStream_t stream) {
   return hipSuccess;
 }
 
+hipError_t lds_moe_align(const int32_t* ids, int32_t* tiles, int32_t* n_tiles,
+                         int32_t* perm, int64_t P, int E, int TM,
+                         hipStream_t stream) {
+  hipLaunchKernelGGL(moe_align_kernel, dim3(1), dim3(MOE_MAX_EXPERTS), 0,
+                     stream, ids, tiles, n_tiles, perm, (int)P, E, TM);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t lds_moe_combine(const float* y2, void* y, int T, int H, int k,
+                           hipStream_t stream) {
+  const int64_t n_oct = (int64_t)T * H / 8;
+  hipLaunchKernelGGL(moe_combine_kernel,
+                     dim3((uint32_t)((n_oct + MOE_THREADS - 1) / MOE_THREADS)),
+                     dim3(MOE_THREADS), 0, stream, y2, (short*)y, n_oct, H, k);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
 // The work list in front of the two GEMMs and the slot sum behind them, for
 // any weight format: A is MoeFfnArgs, MoeFfnMxfp4Args or MoeFfnFp8Args.
 template <class A, class F>
@@ -1058,19 +1077,12 @@ hipError_t moe_ffn_launch(const A& a, F&& gemms, hipStream_t stream) {
   if (a.T == 0) return hipSuccess;
   const int64_t P = (int64_t)a.T * a.k;
   const uint32_t n_tiles = (uint32_t)moe_tile_bound(P, a.E, a.mb);
-  hipLaunchKernelGGL(moe_align_kernel, dim3(1), dim3(MOE_MAX_EXPERTS), 0,
-                     stream, a.ids, a.tiles, a.n_tiles, a.perm, (int)P, a.E,
-                     16 * a.mb);
-  HIP_CHECK_LAST();
+  hipError_t err = lds_moe_align(a.ids, a.tiles, a.n_tiles, a.perm, P, a.E,
+                                 16 * a.mb, stream);
+  if (err != hipSuccess) return err;
   if (!gemms(n_tiles)) return hipErrorInvalidValue;
   HIP_CHECK_LAST();
-  const int64_t n_oct = (int64_t)a.T * a.H / 8;
-  hipLaunchKernelGGL(moe_combine_kernel,
-                     dim3((uint32_t)((n_oct + MOE_THREADS - 1) / MOE_THREADS)),
-                     dim3(MOE_THREADS), 0, stream, a.y2, (short*)a.y, n_oct,
-                     a.H, a.k);
-  HIP_CHECK_LAST();
-  return hipSuccess;
+  return lds_moe_combine(a.y2, a.y, a.T, a.H, a.k, stream);
 }
 
 hipError_t lds_moe_ffn(const MoeFfnArgs& a, hipStream_t stream) {

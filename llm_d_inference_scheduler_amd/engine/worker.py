@@ -412,7 +412,8 @@ class EngineWorker:
                  max_lora_rank: int = 16,
                  weight_dtype: str = "auto",
                  expert_dtype: str = "auto",
-                 activation_dtype: str = "auto"):
+                 activation_dtype: str = "auto",
+                 expert_activation_dtype: str = "auto"):
         """weight_dtype "fp8" stores the four projections of every layer as
         weight-only fp8 with one scale per output channel (DEVELOPMENT.md
         "fp8 weights"), "mxfp4" as OCP Microscaling FP4, e2m1 codes with one
@@ -435,8 +436,15 @@ class EngineWorker:
         scale, on the fp8 MFMA (DEVELOPMENT.md "fp8 activations"). The
         quantisation a row sees then depends on the size of the batch it
         ran in. On an MoE model it covers wqkv and wo; the experts are
-        untouched. "auto" and "bf16" keep bf16 activations. Both ranks of a
-        P/D pair must use the same value.
+        untouched (expert_activation_dtype is their option). "auto" and
+        "bf16" keep bf16 activations. Both ranks of a P/D pair must use the
+        same value.
+
+        expert_activation_dtype "fp8" (with expert_dtype "fp8" only; anything
+        else is a ValueError) runs the experts of batches above the skinny
+        kernels' crossover with fp8 activations on the fp8 MFMA
+        (DEVELOPMENT.md "Mixture of experts"), under the same caveat. "auto"
+        and "bf16" keep bf16 activations in the experts.
 
         kv_scales selects the per-head scales of an fp8 KV cache
         (KVPool): "none" (unscaled direct cast), "calibrate" (run
@@ -462,6 +470,12 @@ class EngineWorker:
         if activation_dtype == "fp8" and weight_dtype != "fp8":
             raise ValueError('activation_dtype "fp8" needs weight_dtype '
                              f'"fp8", got weight_dtype {weight_dtype!r}')
+        if expert_activation_dtype not in ("auto", "bf16", "fp8"):
+            raise ValueError("unknown expert_activation_dtype "
+                             f"{expert_activation_dtype!r}")
+        if expert_activation_dtype == "fp8" and expert_dtype != "fp8":
+            raise ValueError('expert_activation_dtype "fp8" needs '
+                             f'expert_dtype "fp8", got {expert_dtype!r}')
         if expert_dtype != "auto" and not config.num_experts:
             raise ValueError(f"expert_dtype {expert_dtype!r} needs an MoE "
                              "model: a dense model has no experts")
@@ -498,6 +512,7 @@ class EngineWorker:
             if expert_dtype != "bf16":
                 self.model.quantize_experts(expert_dtype)
         self.model.set_activation_dtype(activation_dtype)
+        self.model.set_expert_activation_dtype(expert_activation_dtype)
         self.seed = seed
         self.max_loras = max_loras
         self.adapters: Dict[str, LoraAdapter] = {}   # registered, on the host

@@ -171,9 +171,17 @@ class LlamaRunner:
         # bf16 scratch below is never allocated
         self.activation_dtype = "bf16"
         self._fp8_scratch: Dict[int, torch.Tensor] = {}
-        # ops.moe_ffn / moe_ffn_mxfp4 / moe_ffn_fp8 scratch, one per stream, sized by
-        # the largest T seen
+        # ops.moe_ffn / moe_ffn_mxfp4 / moe_ffn_fp8 / moe_ffn_fp8_a8 scratch,
+        # one per stream, sized by the largest T seen
         self._moe_scratch: Dict[int, torch.Tensor] = {}
+        # "fp8" (set_expert_activation_dtype): fp8 experts at batches of
+        # more than _moe_a8_min_rows mean rows per expert (T k / E) go
+        # through ops.moe_ffn_fp8_a8, the others through ops.moe_ffn_fp8. 8
+        # is the measured crossover on a Qwen3-30B-A3B layer: at 8 rows an
+        # expert the two ops tie (0.99x), at 16 moe_ffn_fp8_a8 leads 1.15x
+        # (profiles/moe_fp8_a8.md)
+        self.expert_activation_dtype = "bf16"
+        self._moe_a8_min_rows = 8
 
     def weight_bytes(self) -> int:
         tensors = [self.embed, self.lm_head, self.final_norm]
@@ -237,7 +245,8 @@ class LlamaRunner:
         and torch.matmul. Needs quantize_weights("fp8") first. Smaller
         batches keep the weight-only kernel, so the quantisation a row sees
         depends on the size of the batch it ran in. The experts of an MoE
-        model are untouched. "auto" and "bf16" change nothing."""
+        model are untouched: set_expert_activation_dtype is their option.
+        "auto" and "bf16" change nothing."""
         if activation_dtype not in ("auto", "bf16", "fp8"):
             raise ValueError(f"unknown activation_dtype {activation_dtype!r}")
         if activation_dtype != "fp8":
@@ -247,6 +256,33 @@ class LlamaRunner:
                 'activation_dtype "fp8" needs weight_dtype "fp8", the '
                 f"weights are {self.weight_dtype}")
         self.activation_dtype = "fp8"
+
+    def set_expert_activation_dtype(self, expert_activation_dtype: str) -> None:
+        """With "fp8" (DEVELOPMENT.md "Mixture of experts") batches of more
+        than _moe_a8_min_rows mean rows per expert run the fp8 experts with
+        fp8 activations: x and silu(g) * u are quantised per row to e4m3 with
+        a dynamic scale and both expert GEMMs run on the fp8 MFMA
+        (ops.moe_ffn_fp8_a8). Needs quantize_experts("fp8") first, and
+        hidden_size and moe_intermediate_size multiples of 64. Smaller
+        batches keep ops.moe_ffn_fp8, so the quantisation a row sees depends
+        on the size of the batch it ran in. "auto" and "bf16" change
+        nothing."""
+        if expert_activation_dtype not in ("auto", "bf16", "fp8"):
+            raise ValueError("unknown expert_activation_dtype "
+                             f"{expert_activation_dtype!r}")
+        if expert_activation_dtype != "fp8":
+            return
+        if self.expert_dtype != "fp8":
+            raise ValueError(
+                'expert_activation_dtype "fp8" needs expert_dtype "fp8", the '
+                f"experts are {self.expert_dtype}")
+        c = self.cfg
+        if c.hidden_size % 64 or c.moe_intermediate_size % 64:
+            raise ValueError(
+                'expert_activation_dtype "fp8" needs hidden_size and '
+                "moe_intermediate_size to be multiples of 64, got "
+                f"{c.hidden_size} and {c.moe_intermediate_size}")
+        self.expert_activation_dtype = "fp8"
 
     def _check_expert_dtype(self, expert_dtype: str, allowed: str) -> None:
         """ValueError unless the experts can become expert_dtype: an MoE model
@@ -349,19 +385,27 @@ class LlamaRunner:
         ids, w = ops.moe_route(x, layer["router"], c.experts_per_token,
                                c.norm_topk_prob)
         # a bf16 tensor, an MXFP4 pair (uint8) or an fp8 pair
-        mx = False
+        mx = a8 = False
         if not isinstance(layer["w13"], tuple):
             ffn, experts = ops.moe_ffn, (layer["w13"], layer["w2"])
         else:
             mx = layer["w13"][0].dtype == torch.uint8
-            ffn = ops.moe_ffn_mxfp4 if mx else ops.moe_ffn_fp8
+            # host arithmetic on the batch size alone: no sync
+            a8 = not mx and self.expert_activation_dtype == "fp8" and \
+                x.shape[0] * c.experts_per_token > \
+                self._moe_a8_min_rows * c.num_experts
+            ffn = ops.moe_ffn_mxfp4 if mx else \
+                ops.moe_ffn_fp8_a8 if a8 else ops.moe_ffn_fp8
             experts = (*layer["w13"], *layer["w2"])
         if not x.is_cuda:
             return ffn(x, *experts, ids, w)
         key = torch.cuda.current_stream(x.device).cuda_stream
-        need = ops.moe_scratch_bytes(x.shape[0], c.experts_per_token,
-                                     c.num_experts, c.hidden_size,
-                                     c.moe_intermediate_size, mxfp4=mx)
+        shape = (x.shape[0], c.experts_per_token, c.num_experts,
+                 c.hidden_size, c.moe_intermediate_size)
+        need = ops.moe_scratch_bytes(*shape, mxfp4=mx)
+        if self.expert_activation_dtype == "fp8":
+            # one buffer serves both ops: the larger of the two needs
+            need = max(need, ops.moe_fp8_a8_scratch_bytes(*shape))
         buf = self._moe_scratch.get(key)
         if buf is None or buf.numel() < need:
             buf = self._moe_scratch[key] = torch.empty(

@@ -98,6 +98,9 @@ class NodeConfig:
     # for batches above the weight-only kernel's crossover; needs
     # weight_dtype fp8); the same on every rank that exchanges KV
     activation_dtype: str = "auto"
+    # auto|bf16|fp8, MoE models only (fp8 = the same for the experts of
+    # prefill-sized batches; needs expert_dtype fp8)
+    expert_activation_dtype: str = "auto"
     # per-head scales of an fp8 cache (engine/worker.py): "none",
     # "calibrate" or the path of a scales JSON. Defaults from the
     # environment variable LLMD_KV_SCALES so a benchmark run can select
@@ -235,7 +238,8 @@ class NodeRunner:
             kv_calib_tokens=cfg.kv_calib_tokens,
             max_loras=cfg.max_loras, max_lora_rank=cfg.max_lora_rank,
             weight_dtype=cfg.weight_dtype, expert_dtype=cfg.expert_dtype,
-            activation_dtype=cfg.activation_dtype)
+            activation_dtype=cfg.activation_dtype,
+            expert_activation_dtype=cfg.expert_activation_dtype)
         if cfg.lora_adapters and cfg.max_loras <= 0:
             raise ValueError("lora_adapters needs max_loras >= 1")
         for name, spec in cfg.lora_adapters.items():

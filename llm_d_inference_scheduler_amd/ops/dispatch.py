@@ -362,6 +362,29 @@ def moe_ffn_fp8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
     return ref.moe_ffn_fp8(x, w13q, w13s, w2q, w2s, ids, w)
 
 
+def moe_fp8_a8_scratch_bytes(T: int, k: int, E: int, H: int, I: int) -> int:
+    """Bytes of the scratch ops.moe_ffn_fp8_a8 takes for T tokens."""
+    return hip_ops().moe_fp8_a8_scratch_bytes(T, k, E, H, I)
+
+
+def moe_ffn_fp8_a8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
+                   w2q: torch.Tensor, w2s: torch.Tensor, ids: torch.Tensor,
+                   w: torch.Tensor, scratch: Optional[torch.Tensor] = None,
+                   act_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_ffn_fp8 with fp8 activations (DEVELOPMENT.md "Mixture of
+    experts"): x and the activation are quantised per row by
+    quantize_rows_fp8 and both expert GEMMs run on the fp8 MFMA, the row
+    scale applied to the fp32 sum first, then the channel scale. The
+    arguments of moe_ffn_fp8 with H % 64 == 0 and I % 64 == 0. scratch (GPU
+    only): at least moe_fp8_a8_scratch_bytes. act_out: a [T k, I] bf16 tensor
+    that receives bf16(silu(g) * u) of pair t k + j."""
+    if _use_hip(x):
+        return _ext.moe_ffn_fp8_a8(x, w13q, w13s, w2q, w2s, ids, w, scratch,
+                                   0, act_out)
+    return ref.moe_ffn_fp8_a8(x, w13q, w13s, w2q, w2s, ids, w,
+                              act_out=act_out)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

@@ -915,6 +915,37 @@ def moe_ffn_fp8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
                    dequant_experts_fp8(w2q, w2s), ids, w)
 
 
+def moe_ffn_fp8_a8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
+                   w2q: torch.Tensor, w2s: torch.Tensor, ids: torch.Tensor,
+                   w: torch.Tensor,
+                   act_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_ffn_fp8 with both activations quantised per row by
+    quantize_rows_fp8: the fp32 sums of codes times the row scale, then the
+    channel scale. act = bf16(silu(g) * u) is quantised per (token, slot)
+    pair; act_out [T k, I], if given, receives it at row t k + j."""
+    T, H = x.shape
+    I, k = w13q.shape[1] // 2, ids.shape[1]
+    xq, sx = quantize_rows_fp8(x)
+    xf = xq.float()
+    y2 = torch.zeros(T, k, H, dtype=torch.float32, device=x.device)
+    for e in range(w13q.shape[0]):
+        t, j = (ids == e).nonzero(as_tuple=True)
+        if t.numel() == 0:
+            continue
+        gu = (xf[t] @ w13q[e].float().t()) * sx[t][:, None] * w13s[e][None, :]
+        g, u = gu.split(I, dim=-1)
+        act = (g * torch.sigmoid(g) * u).to(x.dtype)
+        if act_out is not None:
+            act_out[t * k + j] = act.to(act_out.dtype)
+        aq, sa = quantize_rows_fp8(act)
+        y2[t, j] = (aq.float() @ w2q[e].float().t()) * sa[:, None] * \
+            w2s[e][None, :] * w[t, j].float()[:, None]
+    y = y2[:, 0]
+    for j in range(1, k):
+        y = y + y2[:, j]
+    return y.to(x.dtype)
+
+
 _PREFIX_MODEL = PrefixModel()
 hash_prompts = _PREFIX_MODEL.hash_prompts
 table_update = _PREFIX_MODEL.table_update

@@ -58,6 +58,11 @@ def parse_args(argv=None):
                         "dynamic e4m3 activations on the fp8 MFMA; the "
                         "quantisation a row sees then depends on the size "
                         "of its batch")
+    p.add_argument("--expert-activation-dtype", default="auto",
+                   choices=["auto", "bf16", "fp8"],
+                   help="MoE models, fp8 (needs --expert-dtype fp8): the "
+                        "experts of prefill-sized batches run with per-row "
+                        "dynamic e4m3 activations on the fp8 MFMA")
     p.add_argument("--kv-scales", default=None,
                    help='per-head scales of an fp8 KV cache: "none", '
                         '"calibrate" (synthetic tokens at start-up) or the '
@@ -126,6 +131,7 @@ def build_node(args):
         kv_cache_dtype=args.kv_dtype, weight_dtype=args.weight_dtype,
         expert_dtype=args.expert_dtype,
         activation_dtype=args.activation_dtype,
+        expert_activation_dtype=args.expert_activation_dtype,
         flow_control=args.flow_control,
         decode_chunk_tokens=args.decode_chunk_tokens or None,
         seed=args.seed, max_loras=args.max_loras,

@@ -44,6 +44,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/linear_fp8_a8.hip",
         "csrc/hip/linear_mxfp4.hip",
         "csrc/hip/moe.hip",
+        "csrc/hip/moe_fp8_a8.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],

@@ -2,7 +2,7 @@
 Qwen3-30B-A3B shapes (results: profiles/moe.md).
 
     python tools/moe_bench.py [--rounds 7] [--copies 8]
-                              [--weights mxfp4|fp8]
+                              [--weights mxfp4|fp8|fp8_a8]
 
 One layer: H 2048, 128 experts of I 768, 8 a token, for T in {1, 16, 64, 256,
 1024, 4096}. Arms, timed in one process in interleaved rounds (arm order
@@ -44,6 +44,18 @@ ops.ref.quantize_experts_fp8:
 `floor` is 1 byte a weight plus the fp32 scales of the touched experts. The
 fp8 output is checked against the float64 bound on the float64 experts
 wq * scale before each T is timed, the bf16 arm on its own bf16 experts.
+
+--weights fp8_a8 (results: profiles/moe_fp8_a8.md) times the two ops the
+runner chooses between on fp8 experts, for T in {64, 128, ..., 4096}:
+  fp8_a8   ops.moe_route, then ops.moe_ffn_fp8_a8: fp8 activations, LDS-staged
+           tiles on the fp8 MFMA
+  fp8      ops.moe_route, then ops.moe_ffn_fp8: bf16 activations, the skinny
+           kernels
+`rows` is the mean rows per expert T k / E, the unit of the runner's
+_moe_a8_min_rows, and `ratio` fp8 over fp8_a8. At T = 64 the fp8_a8 output is
+judged by the two-stage float64 bound of tests/moe_fp8_a8_cases.py; at every
+larger T its first 64 rows must be those bits again (a row's bits do not
+depend on the batch).
 """
 import argparse
 import json
@@ -58,12 +70,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import moe_cases  # noqa: E402
+import moe_fp8_a8_cases  # noqa: E402
 from llm_d_inference_scheduler_amd import ops  # noqa: E402
 from llm_d_inference_scheduler_amd.models.configs import (  # noqa: E402
     QWEN3_30B_A3B)
 
 DEV = "cuda"
 TS = (1, 16, 64, 256, 1024, 4096)
+TS_A8 = (64, 128, 256, 512, 1024, 2048, 4096)
 WINDOW_US = 10000.0
 HBM_BYTES_PER_US = 8e6
 
@@ -132,7 +146,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--copies", type=int, default=8)
-    ap.add_argument("--weights", choices=["bf16", "mxfp4", "fp8"], default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "mxfp4", "fp8", "fp8_a8"],
+                    default="bf16")
     args = ap.parse_args()
     ops.hip_ops()
     c = QWEN3_30B_A3B
@@ -145,6 +160,8 @@ def main():
     w13s = [randn(E, 2 * I, H).mul_(0.02).bfloat16() for _ in range(n)]
     w2s = [randn(E, H, I).mul_(0.02).bfloat16() for _ in range(n)]
     expert_bytes = 3 * I * H * 2
+    if args.weights == "fp8_a8":
+        return main_fp8_a8(args, routers, w13s, w2s, randn)
     if args.weights != "bf16":
         return main_quantised(args, routers, w13s, w2s, randn)
     for T in TS:
@@ -237,6 +254,59 @@ def main_quantised(args, routers, w13s, w2s, randn):
             T=T, H=H, I=I, E=E, k=k, copies=n, experts=round(touched, 1),
             floor=floor(bits, scale_bytes), floor_bf16=floor(16, 0),
             **bench(fns, args.rounds))), flush=True)
+        del xs, scratch
+
+
+def main_fp8_a8(args, routers, w13s, w2s, randn):
+    """--weights fp8_a8: ops.moe_ffn_fp8_a8 against ops.moe_ffn_fp8 on the
+    same fp8 experts."""
+    n, (E, _, H), I = args.copies, w13s[0].shape, w2s[0].shape[2]
+    k = QWEN3_30B_A3B.experts_per_token
+    quantize = ops.ref.quantize_experts_fp8
+    q13s, q2s = [], []
+    for i in range(n):
+        q13s.append(quantize(w13s[i]))
+        q2s.append(quantize(w2s[i]))
+        w13s[i] = w2s[i] = None
+    x0 = randn(max(TS_A8), H).bfloat16()    # copy 0's x at every T: a prefix
+    y_first = None
+    for T in TS_A8:
+        xs = [x0[:T]] + [randn(T, H).bfloat16() for _ in range(n - 1)]
+        scratch = {
+            "fp8_a8": ops.moe_fp8_a8_scratch_bytes(T, k, E, H, I),
+            "fp8": ops.moe_scratch_bytes(T, k, E, H, I)}
+        scratch = {a: torch.empty(b, dtype=torch.uint8, device=DEV)
+                   for a, b in scratch.items()}
+
+        def a8(i, **kw):
+            ids, w = ops.moe_route(xs[i], routers[i], k, True)
+            return ops.moe_ffn_fp8_a8(xs[i], *q13s[i], *q2s[i], ids, w,
+                                      scratch["fp8_a8"], **kw)
+
+        def fp8(i):
+            ids, w = ops.moe_route(xs[i], routers[i], k, True)
+            return ops.moe_ffn_fp8(xs[i], *q13s[i], *q2s[i], ids, w,
+                                   scratch["fp8"])
+
+        if y_first is None:
+            ids, w = ops.moe_route(xs[0], routers[0], k, True)
+            act = torch.empty(T * k, I, dtype=torch.bfloat16, device=DEV)
+            y_first = a8(0, act_out=act)
+            cpu = [t.cpu() for t in (xs[0], *q13s[0], *q2s[0], ids, w)]
+            dense = tuple(wq.double() * sc.double()[..., None]
+                          for wq, sc in ((cpu[1], cpu[2]), (cpu[3], cpu[4])))
+            e1, e2 = moe_fp8_a8_cases.excess(y_first.cpu(), act.cpu(), cpu,
+                                             dense)
+            if e1 > 0 or e2 > 0:
+                raise SystemExit(f"T={T} fp8_a8: excess {e1:.3e} {e2:.3e}")
+            print(f"# T={T} fp8_a8 excess {e1:.3e} {e2:.3e}", flush=True)
+        elif not torch.equal(a8(0)[:y_first.shape[0]], y_first):
+            raise SystemExit(f"T={T} fp8_a8: the first rows changed")
+        fns = {"fp8_a8": rotating(a8, n), "fp8": rotating(fp8, n)}
+        res = bench(fns, args.rounds)
+        print(json.dumps(dict(
+            T=T, H=H, I=I, E=E, k=k, copies=n, rows=T * k / E, **res,
+            ratio=round(res["fp8"] / res["fp8_a8"], 2))), flush=True)
         del xs, scratch
 
 
