@@ -1,7 +1,8 @@
 // fp8_tile.h — the LDS-staged fp8 operand tile shared by the W8A8 GEMMs
-// (linear_fp8_a8.hip, moe_fp8_a8.hip): the swizzled tile address, a thread's
-// staging registers, the MFMA operand read and the slab loop. The layout and
-// its derivation are in the header of linear_fp8_a8.hip.
+// (linear_fp8_a8.hip, moe_fp8_a8.hip, linear_fp8_block.hip): the swizzled
+// tile address, a thread's staging registers, the MFMA operand read and the
+// slab loop, and the eight-element steps of the activation quantisers. The
+// layout and its derivation are in the header of linear_fp8_a8.hip.
 #pragma once
 #include "hip_common.h"
 #include "launchers.h"
@@ -17,12 +18,40 @@ namespace fp8_tile {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 constexpr int A8_THREADS = 256;
 constexpr int A8_WAVES = A8_THREADS / WAVE;
 constexpr int BK = LINEAR_FP8_A8_BK;     // bytes of K a slab
 constexpr int CHUNKS = BK / 16;          // 16-byte chunks of a tile row
 constexpr int E8M0_ONE = 0x7F7F7F7F;     // scale 2^0 in every byte
+
+// ---- quantiser steps -------------------------------------------------------
+
+__device__ __forceinline__ float absmax8(short8 v, float m) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(bf16_to_f32(v[j])));
+  return m;
+}
+
+// 8 bf16 -> 8 e4m3 codes of x / sx, clamped to +-448, in element order
+__device__ __forceinline__ u32x2 quant8(short8 v, float sx) {
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float q = __fdiv_rn(bf16_to_f32(v[j]), sx);
+    f[j] = q > FP8_E4M3_MAX ? FP8_E4M3_MAX
+                            : (q < -FP8_E4M3_MAX ? -FP8_E4M3_MAX : q);
+  }
+  u32x2 o = {0u, 0u};
+  o[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], o[0], false);
+  o[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], o[0], true);
+  o[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], o[1], false);
+  o[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], o[1], true);
+  return o;
+}
+
+// ---- operand tile ----------------------------------------------------------
 
 // the single LDS address function of an operand tile: byte offset of the
 // 16-byte chunk c of row r
@@ -96,17 +125,30 @@ __device__ __forceinline__ i32x8 read_operand(const unsigned char* tile,
   return u.v;
 }
 
+// What gemm_slabs does with an instruction's result. NoPromotion: the MFMA
+// adds into the running sum itself, one scale pair for the whole of K
+// (linear_fp8_a8.hip, moe_fp8_a8.hip). A promoting policy (BlockScales of
+// linear_fp8_block.hip) has per-slab scales: the MFMA goes into a zeroed
+// partial and acc += partial * row_scales(mb)[j]. It provides
+//   fetch(slab)      issue the loads of a slab's scales (no wait)
+//   advance()        the scales fetched last become the current ones
+//   row_scales(mb)   the current scale of this lane's D rows j of row block mb
+struct NoPromotion {
+  static constexpr bool promoted = false;
+};
+
 // acc += A · Bᵀ over the ceil(in / 128) slabs of K, for a workgroup of four
 // waves 2 x 2 whose wave owns WM x WN blocks of 16 x 16 at rows wm of the A
 // tile (32 WM rows) and rows wn of the B tile (32 WN rows). lds holds two
-// stages of (A tile, B tile). The loads of slab s + 1 are issued before the
-// MFMAs of slab s and written to the other stage behind them: one barrier a
-// slab, and every wave is past the last read of lds when this returns.
-template <int WM, int WN>
+// stages of (A tile, B tile). The loads of slab s + 1 (and its scales, under
+// a promoting policy) are issued before the MFMAs of slab s and written to
+// the other stage behind them: one barrier a slab, and every wave is past
+// the last read of lds when this returns.
+template <int WM, int WN, class P>
 __device__ __forceinline__ void gemm_slabs(Staging<WM>& sa, Staging<WN>& sb,
                                            unsigned char* lds,
                                            f32x4 (&acc)[WM][WN], int wm,
-                                           int wn, int in) {
+                                           int wn, int in, P& p) {
   constexpr int A_BYTES = 32 * WM * BK, STAGE = 32 * (WM + WN) * BK;
   const int kc = (threadIdx.x & (CHUNKS - 1)) * 16;  // chunk's k in a slab
 #pragma unroll
@@ -117,8 +159,10 @@ __device__ __forceinline__ void gemm_slabs(Staging<WM>& sa, Staging<WN>& sb,
   const int n_slabs = (in + BK - 1) / BK;
   sa.load(0, kc < in);
   sb.load(0, kc < in);
+  if constexpr (P::promoted) p.fetch(0);
   sa.store(lds);
   sb.store(lds + A_BYTES);
+  if constexpr (P::promoted) p.advance();
   __syncthreads();
   for (int s = 0; s < n_slabs; ++s) {
     const unsigned char* cur = lds + (s & 1) * STAGE;
@@ -128,6 +172,7 @@ __device__ __forceinline__ void gemm_slabs(Staging<WM>& sa, Staging<WN>& sb,
       const bool in_slab = (s + 1) * BK + kc < in;
       sa.load(s + 1, in_slab);
       sb.load(s + 1, in_slab);
+      if constexpr (P::promoted) p.fetch(s + 1);
     }
     i32x8 b[WN];
 #pragma unroll
@@ -136,18 +181,44 @@ __device__ __forceinline__ void gemm_slabs(Staging<WM>& sa, Staging<WN>& sb,
 #pragma unroll
     for (int mb = 0; mb < WM; ++mb) {
       const i32x8 a = read_operand(cur, wm + mb * 16);
+      if constexpr (P::promoted) {
+        const f32x4 rs = p.row_scales(mb);
+        f32x4 part[WN];
 #pragma unroll
-      for (int nb = 0; nb < WN; ++nb)
-        acc[mb][nb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            a, b[nb], acc[mb][nb], 0, 0, 0, E8M0_ONE, 0, E8M0_ONE);
+        for (int nb = 0; nb < WN; ++nb)
+          part[nb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              a, b[nb], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, E8M0_ONE, 0,
+              E8M0_ONE);
+#pragma unroll
+        for (int nb = 0; nb < WN; ++nb)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[mb][nb][j] =
+                __builtin_fmaf(part[nb][j], rs[j], acc[mb][nb][j]);
+      } else {
+#pragma unroll
+        for (int nb = 0; nb < WN; ++nb)
+          acc[mb][nb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              a, b[nb], acc[mb][nb], 0, 0, 0, E8M0_ONE, 0, E8M0_ONE);
+      }
     }
     if (more) {
       sa.store(nxt);
       sb.store(nxt + A_BYTES);
+      if constexpr (P::promoted) p.advance();
     }
     // slab s + 1 is visible, and slab s is free for the loads of s + 2
     __syncthreads();
   }
+}
+
+template <int WM, int WN>
+__device__ __forceinline__ void gemm_slabs(Staging<WM>& sa, Staging<WN>& sb,
+                                           unsigned char* lds,
+                                           f32x4 (&acc)[WM][WN], int wm,
+                                           int wn, int in) {
+  NoPromotion p;
+  gemm_slabs<WM, WN, NoPromotion>(sa, sb, lds, acc, wm, wn, in, p);
 }
 
 }  // namespace fp8_tile

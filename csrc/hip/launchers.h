@@ -227,6 +227,101 @@ struct LinearFp8A8Args {
 
 hipError_t lds_linear_fp8_a8(const LinearFp8A8Args& a, hipStream_t stream);
 
+// ---- linear_fp8_block.hip ------------------------------------------------
+
+// k of one activation group and edge of one weight block: one 16x16x128 fp8
+// MFMA deep, and one slab of the tiled kernel (LINEAR_FP8_A8_BK).
+constexpr int LINEAR_FP8_BLOCK_GROUP = 128;
+inline int linear_fp8_block_groups(int in) {
+  return (in + LINEAR_FP8_BLOCK_GROUP - 1) / LINEAR_FP8_BLOCK_GROUP;
+}
+// The activation scales live on the device as [G, Tp], group-major with the
+// row count rounded up to 4: a lane's four D rows of a group are one aligned
+// 16-byte load, and a tile's rows of a slab are contiguous. Entries of the
+// rows T .. Tp - 1 are never written and never reach a stored element.
+__host__ __device__ inline int linear_fp8_block_tp(int T) {
+  return (T + 3) & ~3;
+}
+
+// The skinny kernel splits K across workgroups by the rule of
+// linear_fp8_k_splits, with the same constants (set by reasoning there, not
+// re-measured here): until a launch at BN = 32 holds LINEAR_FP8_SPLIT_WGS
+// workgroups, while a split keeps LINEAR_FP8_SPLIT_MIN_K k (8 groups, two a
+// wave), 8 splits at the most. A function of (in, out) alone, so a row's
+// bits do not depend on what else is launched.
+inline int linear_fp8_block_k_splits(int in, int out) {
+  return linear_fp8_k_splits(in, out);
+}
+
+constexpr int LINEAR_FP8_BLOCK_SKINNY = 1;
+// Up to this many rows the skinny kernel always serves: the tiled kernel
+// issues the four row blocks of a 64-row tile whatever T is and moves both
+// operands through LDS. Measured at T = 1, 16 and 32 on the Llama-3-8B and
+// Qwen3-32B projections (profiles/linear_fp8_block.md): the skinny kernel
+// leads the 64 tile 1.17x to 5.5x on every one, 1.17x to 5.1x at 32.
+constexpr int LINEAR_FP8_BLOCK_SKINNY_ALWAYS_T = 32;
+// Above that, up to this many rows, the skinny kernel serves while the 64 x
+// 64 grid of the tiled kernel would leave CUs idle (fewer than
+// LINEAR_FP8_A8_FILL_WGS = 256 tiles): the tiled kernel has no K split, the
+// skinny one re-reads the weights once per 64 rows but keeps every CU
+// busy. Measured on the same projections: at T = 64 the 64 tile leads only
+// where out >= 28672 (448 tiles and more: 45.2 against 50.2 us, 104.6
+// against 109.2); at T = 128 the skinny kernel leads at out = 4096 .. 6144
+// (128 to 192 tiles: 27.0 against 39.5 us, 33.8 against 39.8, 48.7 against
+// 122.6) and trails from out = 10240 on (320 tiles: 52.0 against 49.1); at
+// T = 256 and out = 4096 (256 tiles) it trails on wo (42.4 against 40.2).
+// The rule cannot see `in`: on the deep wdown shapes the skinny kernel still
+// leads at T = 256 (86.9 against 123.2 us), which this rule gives away. 256
+// is the largest T at which the skinny kernel was timed; T from 33 to 63 was
+// not timed and goes by the fill count as 64 does.
+constexpr int LINEAR_FP8_BLOCK_SKINNY_MAX_T = 256;
+
+// Kernel of the block-scaled linear by (T, out) alone: the skinny kernel
+// (LINEAR_FP8_BLOCK_SKINNY) or the 64 tile. The 128 tile is kept as a
+// measurement arm, reachable through the binding's `kernel` argument and
+// tested there, but never picked: with the scaled adds in its slab loop it
+// trails the 64 tile at every measured shape, the largest grids included
+// (Qwen3-32B wgate_up at T = 4096, 12800 large tiles: 3763 against 3070
+// us), so the fill reasoning of linear_fp8_a8_tile does not carry over. It
+// is the arm a cheaper promotion is to be judged against. The skinny and
+// the tiled kernel sum the groups of K in different orders: a row's bits
+// may differ between launches that this rule sends to different kernels,
+// never within either kernel.
+inline int linear_fp8_block_kernel_for(int T, int out) {
+  if (T <= LINEAR_FP8_BLOCK_SKINNY_ALWAYS_T) return LINEAR_FP8_BLOCK_SKINNY;
+  const int64_t tiles = (int64_t)((T + 63) / 64) * ((out + 63) / 64);
+  if (T <= LINEAR_FP8_BLOCK_SKINNY_MAX_T && tiles < LINEAR_FP8_A8_FILL_WGS)
+    return LINEAR_FP8_BLOCK_SKINNY;
+  return 64;
+}
+
+// xq[m, k] = e4m3(clamp(x[m, k] / sx[m, k / 128], +-448)), sx[m, g] =
+// absmax(x[m, 128 g .. 128 g + 127]) / 448 (1 for a zero group), written to
+// sx[g * Tp + m], Tp = linear_fp8_block_tp(T): x [T, in] bf16, in % 64 == 0
+// (the last group may be 64 wide), x and xq 16-byte aligned.
+hipError_t lds_quantize_groups_fp8(const void* x, void* xq, float* sx, int T,
+                                   int in, hipStream_t stream);
+
+// y[m, n] = bf16(sum_g sx[m, g] * scale[n / 128, g] * sum_{k in g}
+// float(xq[m, k]) * float(wq[n, k])), fp32 sums on the fp8 MFMA.
+struct LinearFp8BlockArgs {
+  const void* xq;       // [T, in] OCP e4m3, in % 64 == 0, 16-byte aligned
+  const float* sx;      // [G, Tp] as lds_quantize_groups_fp8 writes it,
+                        // 16-byte aligned
+  const void* wq;       // [out, in] OCP e4m3, out % 16 == 0, 16-byte aligned
+  const float* scale;   // [ceil(out / 128), G]
+  void* y;              // [T, out] bf16, 16-byte aligned
+  float* part;          // [n_split, T, out] fp32 scratch of the skinny
+                        // kernel; unread if n_split is 1
+  int T, in, out;
+  int n_split;          // linear_fp8_block_k_splits(in, out)
+  int kernel;           // linear_fp8_block_kernel_for(T, out), or forced:
+                        // 1, 64 or 128
+};
+
+hipError_t lds_linear_fp8_block(const LinearFp8BlockArgs& a,
+                                hipStream_t stream);
+
 // ---- linear_mxfp4.hip ----------------------------------------------------
 
 // k a wave consumes per step: one 32-wide MX group a lane group, four MFMAs.

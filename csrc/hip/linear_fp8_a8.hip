@@ -76,34 +76,12 @@
 namespace {
 
 using namespace fp8_tile;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 // ---- quantiser -----------------------------------------------------------
+// absmax8 and quant8 are in fp8_tile.h, shared with the group quantiser of
+// linear_fp8_block.hip.
 
 constexpr int QUANT_HELD = 8;  // chunks a thread keeps: 256 * 8 * 8 = 16384 k
-
-__device__ __forceinline__ float absmax8(short8 v, float m) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(bf16_to_f32(v[j])));
-  return m;
-}
-
-// 8 bf16 -> 8 e4m3 codes of x / sx, clamped to +-448, in element order
-__device__ __forceinline__ u32x2 quant8(short8 v, float sx) {
-  float f[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float q = __fdiv_rn(bf16_to_f32(v[j]), sx);
-    f[j] = q > FP8_E4M3_MAX ? FP8_E4M3_MAX
-                            : (q < -FP8_E4M3_MAX ? -FP8_E4M3_MAX : q);
-  }
-  u32x2 o = {0u, 0u};
-  o[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], o[0], false);
-  o[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], o[0], true);
-  o[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], o[1], false);
-  o[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], o[1], true);
-  return o;
-}
 
 __global__ __launch_bounds__(A8_THREADS) void quantize_rows_fp8_kernel(
     const short* __restrict__ x, unsigned char* __restrict__ xq,

@@ -750,6 +750,79 @@ torch::Tensor linear_fp8_a8(torch::Tensor x, torch::Tensor wq,
   return y;
 }
 
+// ---- fp8 block scales ----
+
+// (xq [T, in] e4m3, sx in the device layout [G, Tp] of launchers.h): the
+// per-group dynamic quantisation of x.
+std::tuple<torch::Tensor, torch::Tensor> quantize_groups_device(
+    const torch::Tensor& x, int T, int in) {
+  auto xq = torch::empty({T, in}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto sx = torch::empty({linear_fp8_block_groups(in),
+                          linear_fp8_block_tp(T)},
+                         x.options().dtype(torch::kFloat32));
+  CHECK_HIP(lds_quantize_groups_fp8(x.data_ptr(), xq.data_ptr(),
+                                    sx.data_ptr<float>(), T, in,
+                                    cur_stream()));
+  return {xq, sx};
+}
+
+// (xq [T, in] e4m3, sx [T, G] fp32), G = ceil(in / 128): one dynamic scale
+// per row and 128-wide group of K, the bytes of ops.ref.quantize_groups_fp8.
+// The GEMMs read the scales group-major; this returns them as documented.
+std::tuple<torch::Tensor, torch::Tensor> quantize_groups_fp8(torch::Tensor x) {
+  const auto [T, in] = check_fp8_rows(x);
+  auto [xq, sx] = quantize_groups_device(x, T, in);
+  return {xq, sx.slice(1, 0, T).t().contiguous()};
+}
+
+// y = bf16(sum_g sx[:, g] * scale[n / 128, g] * (xq_g · wq_gᵀ)) with fp32
+// sums on the fp8 MFMA: x [T, in] bf16, quantised per group here, against a
+// block-scaled fp8 weight (DEVELOPMENT.md "fp8 block scales"). kernel is the
+// launch geometry, for measurement and tests only: 0 is what serves
+// (linear_fp8_block_kernel_for) and what ops.linear_fp8_block always passes,
+// 1 the skinny kernel, 64 and 128 the tiles; the 128 tile is a measurement
+// arm only, the serving rule never picks it. The tile never changes a bit of
+// y; the skinny kernel sums the groups in another order than the tiles.
+// check_fp8_rows bounds T by GRID_YZ_MAX * 64, which keeps grid.y of every
+// variant legal (64-row tiles at the least).
+torch::Tensor linear_fp8_block(torch::Tensor x, torch::Tensor wq,
+                               torch::Tensor scale, int64_t kernel) {
+  const auto [T, in] = check_fp8_rows(x);
+  check_tensor(wq, "wq", x, "x", at::kFloat8_e4m3fn, {ANY, in});
+  TORCH_CHECK(wq.size(0) % 16 == 0, "wq.size(0) must be a multiple of 16, "
+              "got ", wq.size(0));
+  check_aligned16(wq, "wq");
+  LinearFp8BlockArgs a{};
+  a.T = T;
+  a.in = in;
+  a.out = check_int(wq.size(0), 0, INT_MAX, "wq.size(0)");
+  check_tensor(scale, "scale", x, "x", at::kFloat,
+               {(a.out + LINEAR_FP8_BLOCK_GROUP - 1) / LINEAR_FP8_BLOCK_GROUP,
+                linear_fp8_block_groups(in)});
+  TORCH_CHECK(kernel == 0 || kernel == LINEAR_FP8_BLOCK_SKINNY ||
+              kernel == 64 || kernel == 128, "kernel must be 0, 1, 64 or "
+              "128, got ", kernel);
+  a.kernel = kernel ? (int)kernel : linear_fp8_block_kernel_for(a.T, a.out);
+  auto y = torch::empty({a.T, a.out}, x.options());
+  if (a.T == 0 || a.out == 0 || a.in == 0) return y;
+  auto [xq, sx] = quantize_groups_device(x, T, in);
+  a.n_split = a.kernel == LINEAR_FP8_BLOCK_SKINNY
+                  ? linear_fp8_block_k_splits(a.in, a.out) : 1;
+  torch::Tensor part;
+  if (a.n_split > 1) {
+    part = torch::empty({a.n_split, a.T, a.out},
+                        x.options().dtype(torch::kFloat32));
+    a.part = part.data_ptr<float>();
+  }
+  a.xq = xq.data_ptr();
+  a.sx = sx.data_ptr<float>();
+  a.wq = wq.data_ptr();
+  a.scale = scale.data_ptr<float>();
+  a.y = y.data_ptr();
+  CHECK_HIP(lds_linear_fp8_block(a, cur_stream()));
+  return y;
+}
+
 // ---- mxfp4 weights ----
 
 // The (wq, scale) pair of an MXFP4 weight (DEVELOPMENT.md "MXFP4 weights"),
@@ -1414,6 +1487,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(wq [out, in] e4m3, scale [out] fp32) on the fp8 MFMA -> y "
         "[T, out] bf16; tile: measurement knob, never changes y",
         py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("tile") = 0);
+  m.def("quantize_groups_fp8", &quantize_groups_fp8,
+        "x [T, in] bf16 -> (xq [T, in] e4m3, sx [T, ceil(in / 128)] fp32), "
+        "one dynamic scale per row and 128-wide group of K",
+        py::arg("x"));
+  m.def("linear_fp8_block", &linear_fp8_block,
+        "x [T, in] bf16, quantised per 128-wide group to fp8, against a "
+        "block-scaled fp8 weight (wq [out, in] e4m3, scale [ceil(out / 128), "
+        "ceil(in / 128)] fp32) on the fp8 MFMA -> y [T, out] bf16; kernel: "
+        "0 the serving rule, 1 skinny, 64 or 128 a tile",
+        py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("kernel") = 0);
   m.def("linear_mxfp4", &linear_mxfp4,
         "x [T, in] bf16 against an MXFP4 weight (wq [out, in / 2] uint8, "
         "scale [out, in / 32] uint8 e8m0) -> y [T, out] bf16; bn, k_splits: "

@@ -418,7 +418,11 @@ class EngineWorker:
         weight-only fp8 with one scale per output channel (DEVELOPMENT.md
         "fp8 weights"), "mxfp4" as OCP Microscaling FP4, e2m1 codes with one
         e8m0 exponent per 32 values along K (DEVELOPMENT.md "MXFP4
-        weights"); "auto" and "bf16" keep the runner's dtype. An MoE model
+        weights"), "fp8_block" as e4m3 with one fp32 scale per 128 x 128
+        block, multiplied with e4m3 activations that carry one dynamic scale
+        per token and 128-wide group of K, at every batch size
+        (DEVELOPMENT.md "fp8 block scales"); "auto" and "bf16" keep the
+        runner's dtype. An MoE model
         takes "mxfp4" only, which stores its experts as MXFP4 too
         (DEVELOPMENT.md "Mixture of experts"); the router stays in the
         runner's dtype. Both ranks of a P/D pair must use the same value.
@@ -428,7 +432,9 @@ class EngineWorker:
         then governs wqkv and wo alone: "fp8" with weight_dtype "fp8" is the
         all-fp8 MoE model, "mxfp4" with weight_dtype "auto" MXFP4 experts
         under bf16 attention. "auto" is the rule above, under which
-        weight_dtype "fp8" alone on an MoE model is an error.
+        weight_dtype "fp8" or "fp8_block" alone on an MoE model is an
+        error, and "fp8_block" is no expert_dtype: block-scaled experts are
+        not built.
 
         activation_dtype "fp8" (with weight_dtype "fp8" only; anything else
         is a ValueError) runs batches above the weight-only kernel's
@@ -437,8 +443,9 @@ class EngineWorker:
         quantisation a row sees then depends on the size of the batch it
         ran in. On an MoE model it covers wqkv and wo; the experts are
         untouched (expert_activation_dtype is their option). "auto" and
-        "bf16" keep bf16 activations. Both ranks of a P/D pair must use the
-        same value.
+        "bf16" keep bf16 activations. weight_dtype "fp8_block" implies fp8
+        activations: "auto" and "fp8" change nothing there, and "bf16" is a
+        ValueError. Both ranks of a P/D pair must use the same value.
 
         expert_activation_dtype "fp8" (with expert_dtype "fp8" only; anything
         else is a ValueError) runs the experts of batches above the skinny
@@ -467,9 +474,11 @@ class EngineWorker:
             raise ValueError(f"unknown expert_dtype {expert_dtype!r}")
         if activation_dtype not in ("auto", "bf16", "fp8"):
             raise ValueError(f"unknown activation_dtype {activation_dtype!r}")
-        if activation_dtype == "fp8" and weight_dtype != "fp8":
+        if activation_dtype == "fp8" and \
+                weight_dtype not in ("fp8", "fp8_block"):
             raise ValueError('activation_dtype "fp8" needs weight_dtype '
-                             f'"fp8", got weight_dtype {weight_dtype!r}')
+                             '"fp8" (or "fp8_block", which implies it), got '
+                             f'weight_dtype {weight_dtype!r}')
         if expert_activation_dtype not in ("auto", "bf16", "fp8"):
             raise ValueError("unknown expert_activation_dtype "
                              f"{expert_activation_dtype!r}")

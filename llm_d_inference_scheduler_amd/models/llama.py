@@ -162,6 +162,8 @@ class LlamaRunner:
         # rows go through ops.linear_fp8 / ops.linear_mxfp4, larger ones
         # through a dequantised bf16 copy and torch.matmul (crossovers:
         # profiles/linear_fp8.md, profiles/linear_mxfp4.md)
+        # "fp8_block" pairs (a 2-D fp32 scale) go through
+        # ops.linear_fp8_block at every batch size
         self.weight_dtype = "bf16"
         self.expert_dtype = "bf16"     # w13 and w2 (quantize_experts)
         self._fp8_kernel_max_t = 128
@@ -196,9 +198,14 @@ class LlamaRunner:
         """Convert the four projections of every layer in place to a
         weight-only format. "fp8": layer[name] becomes the pair (wq
         [out, in] float8_e4m3fn, scale [out] fp32) of
-        ops.ref.quantize_weight_fp8. "mxfp4": the pair (wq [out, in / 2]
-        uint8, scale [out, in / 32] uint8) of ops.ref.quantize_weight_mxfp4;
-        the two are told apart by wq's dtype. Layer by layer, each bf16
+        ops.ref.quantize_weight_fp8. "fp8_block": the pair (wq [out, in]
+        float8_e4m3fn, scale [ceil(out / 128), ceil(in / 128)] fp32) of
+        ops.ref.quantize_weight_fp8_block, told apart from "fp8" by its 2-D
+        scale; it is multiplied with fp8 activations at every batch size
+        (DEVELOPMENT.md "fp8 block scales"). "mxfp4": the pair (wq
+        [out, in / 2] uint8, scale [out, in / 32] uint8) of
+        ops.ref.quantize_weight_mxfp4, told apart by wq's dtype. Layer by
+        layer, each bf16
         tensor dropped as it is converted. The embedding, lm_head and the
         norms keep the runner's dtype. A quantised runner cannot be
         converted to another format: the bf16 weights are gone.
@@ -209,9 +216,14 @@ class LlamaRunner:
         format, and leaves the experts to quantize_experts."""
         if weight_dtype in ("auto", "bf16"):
             return
-        if weight_dtype not in ("fp8", "mxfp4"):
+        if weight_dtype not in ("fp8", "fp8_block", "mxfp4"):
             raise ValueError(f"unknown weight_dtype {weight_dtype!r}")
         experts = experts and bool(self.cfg.num_experts)
+        if experts and weight_dtype == "fp8_block":
+            raise ValueError(
+                'weight_dtype "fp8_block" alone is not supported for an MoE '
+                "model: block-scaled experts are not built; pass expert_dtype "
+                '"bf16", "fp8" or "mxfp4" and fp8_block covers wqkv and wo')
         if experts and weight_dtype != "mxfp4":
             raise ValueError(
                 f"weight_dtype {weight_dtype!r} alone is not supported for an "
@@ -227,8 +239,9 @@ class LlamaRunner:
         if self.device.type == "cuda" and self.dtype != torch.bfloat16:
             raise ValueError(f"{weight_dtype} weights on the GPU need a bf16 "
                              "runner")
-        quantize = ops_ref.quantize_weight_fp8 if weight_dtype == "fp8" \
-            else ops_ref.quantize_weight_mxfp4
+        quantize = {"fp8": ops_ref.quantize_weight_fp8,
+                    "fp8_block": ops_ref.quantize_weight_fp8_block,
+                    "mxfp4": ops_ref.quantize_weight_mxfp4}[weight_dtype]
         for layer in self.layers:
             for name in LORA_TARGETS:
                 if name in layer:
@@ -246,9 +259,20 @@ class LlamaRunner:
         batches keep the weight-only kernel, so the quantisation a row sees
         depends on the size of the batch it ran in. The experts of an MoE
         model are untouched: set_expert_activation_dtype is their option.
-        "auto" and "bf16" change nothing."""
+        "auto" and "bf16" change nothing. "fp8_block" weights are a W8A8
+        format by definition: "auto" and "fp8" change nothing there, and
+        "bf16" is a ValueError."""
         if activation_dtype not in ("auto", "bf16", "fp8"):
             raise ValueError(f"unknown activation_dtype {activation_dtype!r}")
+        if self.weight_dtype == "fp8_block":
+            if activation_dtype == "bf16":
+                raise ValueError(
+                    'activation_dtype "bf16" is not available with '
+                    'weight_dtype "fp8_block": the format is defined with '
+                    "fp8 activations, one scale per token and 128-wide "
+                    "group, and no kernel multiplies its weights by bf16 "
+                    "rows")
+            return
         if activation_dtype != "fp8":
             return
         if self.weight_dtype != "fp8":
@@ -328,13 +352,16 @@ class LlamaRunner:
 
     def dense_layers(self) -> List[Dict[str, torch.Tensor]]:
         """self.layers with the four projections as fp32 [in, out] tensors,
-        an fp8 or mxfp4 pair dequantised exactly: the weights the forward
-        pass applies. MXFP4 and fp8 experts come back as fp32 [E, out, in]."""
+        an fp8, fp8_block or mxfp4 pair dequantised exactly: the weights the
+        forward pass applies. MXFP4 and fp8 experts come back as fp32 [E, out, in]."""
         def dense(w):
             if not isinstance(w, tuple):
                 return w.float()
             if w[0].dtype == torch.uint8:
                 return ops_ref.dequant_mxfp4_weight(*w, dtype=torch.float32)
+            if w[1].dim() == 2:
+                return (w[0].float() * ops_ref.expand_fp8_block_scale(
+                    w[1], *w[0].shape)).t()
             return (w[0].float() * w[1][:, None]).t()
         def experts(w):
             if not isinstance(w, tuple):
@@ -413,12 +440,14 @@ class LlamaRunner:
         return ffn(x, *experts, ids, w, buf)
 
     def _linear(self, x: torch.Tensor, w) -> torch.Tensor:
-        """x @ w for a projection of self.layers: dense, an fp8 pair or an
-        mxfp4 pair (wq is uint8)."""
+        """x @ w for a projection of self.layers: dense, an fp8 pair, an
+        fp8_block pair (the scale is 2-D) or an mxfp4 pair (wq is uint8)."""
         if not isinstance(w, tuple):
             return x @ w
         wq, scale = w
         mx = wq.dtype == torch.uint8
+        if not mx and scale.dim() == 2:
+            return ops.linear_fp8_block(x, wq, scale)
         max_t = self._mxfp4_kernel_max_t if mx else self._fp8_kernel_max_t
         if not mx and self.activation_dtype == "fp8" and x.shape[0] > max_t:
             return ops.linear_fp8_a8(x, wq, scale)

@@ -85,8 +85,10 @@ class NodeConfig:
     kv_blocks: Optional[int] = None
     kv_budget_bytes: int = 8 << 30
     kv_cache_dtype: str = "auto"    # auto|bf16|fp8 (fp8 = OCP e4m3 cache)
-    # auto|bf16|fp8|mxfp4 (fp8 = weight-only e4m3 projections, a scale per
-    # output channel; mxfp4 = e2m1 projections, an e8m0 exponent per 32
+    # auto|bf16|fp8|fp8_block|mxfp4 (fp8 = weight-only e4m3 projections, a
+    # scale per output channel; fp8_block = e4m3 projections with a scale
+    # per 128 x 128 block and e4m3 activations with a scale per token and
+    # 128-wide group of K; mxfp4 = e2m1 projections, an e8m0 exponent per 32
     # values along K, which on an MoE model covers the experts and is the
     # only quantised choice); the same on every rank that exchanges KV
     weight_dtype: str = "auto"
@@ -96,7 +98,9 @@ class NodeConfig:
     expert_dtype: str = "auto"
     # auto|bf16|fp8 (fp8 = per-token dynamic e4m3 activations on the fp8 MFMA
     # for batches above the weight-only kernel's crossover; needs
-    # weight_dtype fp8); the same on every rank that exchanges KV
+    # weight_dtype fp8. weight_dtype fp8_block implies fp8 activations:
+    # auto and fp8 change nothing there, bf16 is an error); the same on
+    # every rank that exchanges KV
     activation_dtype: str = "auto"
     # auto|bf16|fp8, MoE models only (fp8 = the same for the experts of
     # prefill-sized batches; needs expert_dtype fp8)

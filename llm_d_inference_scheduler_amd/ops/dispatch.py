@@ -276,6 +276,31 @@ def linear_fp8_a8(x: torch.Tensor, wq: torch.Tensor,
     return ref.linear_fp8_a8(x, wq, scale)
 
 
+def quantize_groups_fp8(x: torch.Tensor):
+    """x [T, in] bf16 -> (xq [T, in] float8_e4m3fn, sx [T, ceil(in / 128)]
+    fp32), the dynamic per-group quantisation of DEVELOPMENT.md "fp8 block
+    scales": sx[m, g] = absmax of the 128-wide group g of row m / 448 (1 for
+    a zero group), xq = x / sx rounded to e4m3. The bytes of
+    ops.ref.quantize_groups_fp8 on either device. in % 64 == 0."""
+    if _use_hip(x):
+        return _ext.quantize_groups_fp8(x)
+    return ref.quantize_groups_fp8(x)
+
+
+def linear_fp8_block(x: torch.Tensor, wq: torch.Tensor,
+                     scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in] bf16 against a block-scaled fp8 weight (DEVELOPMENT.md "fp8
+    block scales"): wq [out, in] float8_e4m3fn and scale [ceil(out / 128),
+    ceil(in / 128)] fp32 from ops.ref.quantize_weight_fp8_block. x is
+    quantised per group by quantize_groups_fp8 and multiplied on the fp8 MFMA
+    -> y [T, out], y[m, n] = sum_g sx[m, g] * scale[n // 128, g] * sum_{k in
+    g} float(xq[m, k]) * float(wq[n, k]) with fp32 sums. in % 64 == 0,
+    out % 16 == 0."""
+    if _use_hip(x):
+        return _ext.linear_fp8_block(x, wq, scale)
+    return ref.linear_fp8_block(x, wq, scale)
+
+
 def linear_mxfp4(x: torch.Tensor, wq: torch.Tensor,
                  scale: torch.Tensor) -> torch.Tensor:
     """x [T, in] bf16 against an MXFP4 weight (DEVELOPMENT.md "MXFP4

@@ -753,6 +753,76 @@ def linear_fp8_a8(x: torch.Tensor, wq: torch.Tensor,
     return (acc * sx[:, None] * scale[None, :]).to(x.dtype)
 
 
+# ---- fp8 block scales (DEVELOPMENT.md "fp8 block scales") ------------------
+
+FP8_BLOCK = 128   # edge of a weight block and width of an activation group
+
+
+def _fp8_block_scale(amax: torch.Tensor) -> torch.Tensor:
+    return torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+
+
+def quantize_weight_fp8_block(W: torch.Tensor):
+    """W [in, out], applied as x @ W -> (wq [out, in] float8_e4m3fn, scale
+    [ceil(out / 128), ceil(in / 128)] fp32), the recipe of the public
+    block-scaled fp8 checkpoints: scale[b, g] = absmax of the 128 x 128 block
+    (b, g) of Wᵀ / 448 (1 for an all-zero block), wq = Wᵀ / scale rounded to
+    e4m3. Edge blocks are ragged. fp32 division and round-to-nearest-even on
+    either device, so a CPU and a GPU worker hold the same bytes."""
+    wt = W.detach().float().t()
+    n_out, n_in = wt.shape
+    nb, ng = -(-n_out // FP8_BLOCK), -(-n_in // FP8_BLOCK)
+    pad = torch.zeros(nb * FP8_BLOCK, ng * FP8_BLOCK, device=wt.device)
+    pad[:n_out, :n_in] = wt
+    amax = pad.view(nb, FP8_BLOCK, ng, FP8_BLOCK).abs().amax(dim=(1, 3))
+    scale = _fp8_block_scale(amax)
+    wq = (wt / expand_fp8_block_scale(scale, n_out, n_in)).clamp_(
+        -FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return wq.to(torch.float8_e4m3fn).contiguous(), scale.contiguous()
+
+
+def expand_fp8_block_scale(scale: torch.Tensor, n_out: int,
+                           n_in: int) -> torch.Tensor:
+    """scale [NBk, G] -> [out, in]: every element's block scale."""
+    return scale.repeat_interleave(FP8_BLOCK, 0)[:n_out] \
+        .repeat_interleave(FP8_BLOCK, 1)[:, :n_in]
+
+
+def quantize_groups_fp8(x: torch.Tensor):
+    """x [T, K] -> (xq [T, K] float8_e4m3fn, sx [T, ceil(K / 128)] fp32), one
+    dynamic scale per row and 128-wide group of K (the last group may be
+    narrower): sx[m, g] = absmax of the group / 448 (1 for a zero group) and
+    xq = x / sx rounded to e4m3. quantize_rows_fp8 per group: fp32 division
+    and round-to-nearest-even, so a CPU and a GPU worker hold the same
+    bytes."""
+    xf = x.detach().float()
+    T, K = xf.shape
+    ng = -(-K // FP8_BLOCK)
+    pad = torch.zeros(T, ng * FP8_BLOCK, device=xf.device)
+    pad[:, :K] = xf
+    sx = _fp8_block_scale(pad.view(T, ng, FP8_BLOCK).abs().amax(dim=2))
+    xq = (xf / sx.repeat_interleave(FP8_BLOCK, 1)[:, :K]).clamp_(
+        -FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return xq.to(torch.float8_e4m3fn).contiguous(), sx.contiguous()
+
+
+def linear_fp8_block(x: torch.Tensor, wq: torch.Tensor,
+                     scale: torch.Tensor) -> torch.Tensor:
+    """x [T, in], quantised per group by quantize_groups_fp8, against a
+    block-scaled fp8 weight -> [T, out] in x's dtype: y[m, n] = sum_g
+    sx[m, g] * scale[n // 128, g] * sum_{k in g} float(xq[m, k]) *
+    float(wq[n, k]), fp32 sums, groups in order."""
+    xq, sx = quantize_groups_fp8(x)
+    xf, wf = xq.float(), wq.float()
+    n_out, n_in = wf.shape
+    col = scale.repeat_interleave(FP8_BLOCK, 0)[:n_out]      # [out, G]
+    y = torch.zeros(xf.shape[0], n_out, device=x.device)
+    for g in range(sx.shape[1]):
+        k = slice(g * FP8_BLOCK, min((g + 1) * FP8_BLOCK, n_in))
+        y += (xf[:, k] @ wf[:, k].t()) * (sx[:, g, None] * col[None, :, g])
+    return y.to(x.dtype)
+
+
 # ---- MXFP4 weights (DEVELOPMENT.md "MXFP4 weights") -----------------------
 
 MXFP4_GROUP = 32

@@ -37,9 +37,13 @@ def parse_args(argv=None):
     p.add_argument("--kv-dtype", default="auto",
                    choices=["auto", "bf16", "fp8"])
     p.add_argument("--weight-dtype", default="auto",
-                   choices=["auto", "bf16", "fp8", "mxfp4"],
+                   choices=["auto", "bf16", "fp8", "fp8_block", "mxfp4"],
                    help="fp8: weight-only e4m3 projections with one scale "
-                        "per output channel (half the weight bytes); mxfp4: "
+                        "per output channel (half the weight bytes); "
+                        "fp8_block: e4m3 projections with one scale per 128 "
+                        "x 128 block, run with e4m3 activations scaled per "
+                        "token and 128-wide group of K (the recipe of the "
+                        "public block-scaled fp8 checkpoints); mxfp4: "
                         "OCP Microscaling FP4 projections, e2m1 with one "
                         "e8m0 exponent per 32 values (17/64 of the bytes); "
                         "an MoE model takes mxfp4 only, experts included, "
@@ -53,7 +57,9 @@ def parse_args(argv=None):
                         "--weight-dtype")
     p.add_argument("--activation-dtype", default="auto",
                    choices=["auto", "bf16", "fp8"],
-                   help="fp8 (needs --weight-dtype fp8): batches above the "
+                   help="fp8 (needs --weight-dtype fp8; fp8_block weights "
+                        "always run fp8 activations and reject bf16 here): "
+                        "batches above the "
                         "weight-only kernel's crossover run with per-token "
                         "dynamic e4m3 activations on the fp8 MFMA; the "
                         "quantisation a row sees then depends on the size "

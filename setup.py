@@ -42,6 +42,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/lora.hip",
         "csrc/hip/linear_fp8.hip",
         "csrc/hip/linear_fp8_a8.hip",
+        "csrc/hip/linear_fp8_block.hip",
         "csrc/hip/linear_mxfp4.hip",
         "csrc/hip/moe.hip",
         "csrc/hip/moe_fp8_a8.hip",
