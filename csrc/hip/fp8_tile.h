@@ -1,5 +1,6 @@
 // fp8_tile.h — the LDS-staged fp8 operand tile shared by the W8A8 GEMMs
-// (linear_fp8_a8.hip, moe_fp8_a8.hip, linear_fp8_block.hip): the swizzled
+// (linear_fp8_a8.hip, moe_fp8_a8.hip, linear_fp8_block.hip,
+// moe_fp8_block.hip): the swizzled
 // tile address, a thread's staging registers, the MFMA operand read and the
 // slab loop, and the eight-element steps of the activation quantisers. The
 // layout and its derivation are in the header of linear_fp8_a8.hip.
@@ -128,11 +129,15 @@ __device__ __forceinline__ i32x8 read_operand(const unsigned char* tile,
 // What gemm_slabs does with an instruction's result. NoPromotion: the MFMA
 // adds into the running sum itself, one scale pair for the whole of K
 // (linear_fp8_a8.hip, moe_fp8_a8.hip). A promoting policy (BlockScales of
-// linear_fp8_block.hip) has per-slab scales: the MFMA goes into a zeroed
-// partial and acc += partial * row_scales(mb)[j]. It provides
-//   fetch(slab)      issue the loads of a slab's scales (no wait)
-//   advance()        the scales fetched last become the current ones
-//   row_scales(mb)   the current scale of this lane's D rows j of row block mb
+// linear_fp8_block.hip, GatheredScales of moe_fp8_block.hip) has per-slab
+// scales: the MFMA goes into a zeroed partial and acc += partial *
+// row_scales(mb, nb)[j]. It provides
+//   fetch(slab)          issue the loads of a slab's scales (no wait)
+//   advance()            the scales fetched last become the current ones;
+//                        called before the barrier that publishes their slab
+//   row_scales(mb, nb)   the current scale of this lane's D rows j of row
+//                        block mb against column block nb (the dense kernel
+//                        has one weight scale a workgroup and ignores nb)
 struct NoPromotion {
   static constexpr bool promoted = false;
 };
@@ -182,7 +187,6 @@ __device__ __forceinline__ void gemm_slabs(Staging<WM>& sa, Staging<WN>& sb,
     for (int mb = 0; mb < WM; ++mb) {
       const i32x8 a = read_operand(cur, wm + mb * 16);
       if constexpr (P::promoted) {
-        const f32x4 rs = p.row_scales(mb);
         f32x4 part[WN];
 #pragma unroll
         for (int nb = 0; nb < WN; ++nb)
@@ -190,11 +194,13 @@ __device__ __forceinline__ void gemm_slabs(Staging<WM>& sa, Staging<WN>& sb,
               a, b[nb], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, E8M0_ONE, 0,
               E8M0_ONE);
 #pragma unroll
-        for (int nb = 0; nb < WN; ++nb)
+        for (int nb = 0; nb < WN; ++nb) {
+          const f32x4 rs = p.row_scales(mb, nb);
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             acc[mb][nb][j] =
                 __builtin_fmaf(part[nb][j], rs[j], acc[mb][nb][j]);
+        }
       } else {
 #pragma unroll
         for (int nb = 0; nb < WN; ++nb)

@@ -536,6 +536,63 @@ struct MoeFfnFp8A8Args {
 
 hipError_t lds_moe_ffn_fp8_a8(const MoeFfnFp8A8Args& a, hipStream_t stream);
 
+// ---- moe_fp8_block.hip ---------------------------------------------------
+
+// From this many mean rows per expert (P / E) on, the 64-row LDS tiles serve
+// block-scaled experts, below it the 16-row registers-only kernels. The rule
+// started at 16, where an expert's segment still fits one short tile (the
+// reasoning of moe_mb), and was then set to the smallest measured mean at
+// which the 64-row tile is ahead, on a Qwen3-30B-A3B layer (E = 128, k = 8,
+// profiles/moe_fp8_block.md): at T = 1, 0.0625 rows an expert, the 16-row
+// kernels lead (69.2 against 84.3 us); at T = 16, 1 row an expert, the
+// 64-row tiles already do (193.7 against 201.6 us), and at every larger T.
+// Nothing between those two rows was timed.
+constexpr int MOE_FP8_BLOCK_TILED_MIN_ROWS = 1;
+
+// Tile height of the block-scaled expert GEMMs, 16 (the skinny kernels) or
+// 64, from (P, E) alone: no sync. The two families sum the groups of K in
+// different orders, so a pair's bits may differ between launches this rule
+// sends to different families, never within either.
+inline int moe_fp8_block_tile(int64_t P, int E) {
+  return P < (int64_t)E * MOE_FP8_BLOCK_TILED_MIN_ROWS ? 16 : 64;
+}
+
+// moe_ffn on block-scaled fp8 experts with group-scaled fp8 activations
+// (G_K = ceil(K / 128), NBI = ceil(I / 128), NBH = ceil(H / 128)):
+//   (xq, sx) = quantize_groups_fp8(x)
+//   act[p, n] = bf16(silu(g) * u), g = sum_g sx[t, g] * w13s[e, n / 128, g] *
+//               sum_{k in g} xq[t, k] w13q[e, n, k], u the same on row I + n
+//               with w13s[e, NBI + n / 128, g]; p = t k + j, e = ids[p]
+//   (aq, sa) = quantize_groups_fp8(act), per pair row
+//   y2[p, n] = (sum_g sa[p, g] * w2s[e, n / 128, g] * sum_{k in g} aq[p, k]
+//              w2q[e, n, k]) * w[p]
+//   y[t] = bf16(sum_j y2[t k + j])
+struct MoeFfnFp8BlockArgs {
+  const void* x;        // [T, H] bf16, H % 64 == 0, 16-byte aligned
+  const void* w13q;     // [E, 2 I, H] e4m3, 16-byte aligned, I % 64 == 0
+  const float* w13s;    // [E, 2 NBI, G_H]: gate blocks, then up blocks
+  const void* w2q;      // [E, H, I] e4m3, 16-byte aligned
+  const float* w2s;     // [E, NBH, G_I]
+  const int32_t* ids;   // [T, k]
+  const float* w;       // [T, k]
+  void* y;              // [T, H] bf16
+  // scratch, every pointer 16-byte aligned; P = T k
+  void* xq;             // [T, H] e4m3
+  float* sx;            // [G_H, linear_fp8_block_tp(T)]
+  void* act;            // [P, I] bf16, by pair: the scratch's, or act_out
+  void* aq;             // [P, I] e4m3, by pair
+  float* sa;            // [G_I, linear_fp8_block_tp(P)]
+  float* y2;            // [P, H] fp32, by pair
+  int32_t* tiles;       // [moe_tile_bound, 3]
+  int32_t* n_tiles;     // [1]
+  int32_t* perm;        // [moe_tile_bound * tile]
+  int T, H, I, E, k;
+  int tile;             // moe_fp8_block_tile(T * k, E); 16 or 64
+};
+
+hipError_t lds_moe_ffn_fp8_block(const MoeFfnFp8BlockArgs& a,
+                                 hipStream_t stream);
+
 // ---- sampler.hip ---------------------------------------------------------
 
 // What every sampler launch carries: one workgroup per row, no host sync.

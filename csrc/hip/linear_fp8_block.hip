@@ -149,7 +149,7 @@ struct BlockScales {
     for (int mb = 0; mb < WM; ++mb) cur_r[mb] = nxt_r[mb];
     cur_w = nxt_w;
   }
-  __device__ __forceinline__ f32x4 row_scales(int mb) const {
+  __device__ __forceinline__ f32x4 row_scales(int mb, int /*nb*/) const {
     f32x4 r;
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = cur_r[mb][j] * cur_w;

@@ -1241,6 +1241,128 @@ torch::Tensor moe_ffn_fp8_a8(torch::Tensor x, torch::Tensor w13q,
   return y;
 }
 
+// Byte offsets of the scratch arrays of moe_ffn_fp8_block, each 16-byte
+// aligned, and the total (MoeFfnFp8BlockArgs). The work list is sized for
+// either tile height, so a forced tile fits the scratch the rule was given.
+struct MoeBlockScratch {
+  int64_t xq, sx, act, aq, sa, y2, tiles, n_tiles, perm, total;
+};
+
+MoeBlockScratch moe_fp8_block_scratch_layout(int64_t T, int64_t k, int64_t E,
+                                             int64_t H, int64_t I) {
+  const int64_t P = T * k;
+  const int64_t n_tiles = moe_tile_bound(P, (int)E, 1);   // >= that of 64
+  const int64_t rows = std::max(n_tiles * 16,
+                                moe_tile_bound(P, (int)E, 4) * 64);
+  const int64_t GH = linear_fp8_block_groups((int)H);
+  const int64_t GI = linear_fp8_block_groups((int)I);
+  auto up16 = [](int64_t b) { return (b + 15) / 16 * 16; };
+  MoeBlockScratch s{};
+  s.xq = 0;
+  s.sx = s.xq + up16(T * H);
+  s.act = s.sx + up16(GH * linear_fp8_block_tp((int)T) * 4);
+  s.aq = s.act + up16(P * I * 2);
+  s.sa = s.aq + up16(P * I);
+  s.y2 = s.sa + up16(GI * linear_fp8_block_tp((int)P) * 4);
+  s.tiles = s.y2 + up16(P * H * 4);
+  s.n_tiles = s.tiles + up16(n_tiles * 3 * 4);
+  s.perm = s.n_tiles + 16;
+  s.total = s.perm + up16(rows * 4);
+  return s;
+}
+
+int64_t moe_fp8_block_scratch_bytes(int64_t T, int64_t k, int64_t E,
+                                    int64_t H, int64_t I) {
+  check_int(T, 0, INT_MAX / MOE_MAX_TOPK - 4, "T");
+  check_int(k, 1, MOE_MAX_TOPK, "k");
+  check_int(E, 1, MOE_MAX_EXPERTS, "E");
+  check_int(H, 64, INT_MAX, "H");
+  check_int(I, 64, INT_MAX, "I");
+  return moe_fp8_block_scratch_layout(T, k, E, H, I).total;
+}
+
+// moe_ffn on block-scaled fp8 experts with group-scaled fp8 activations
+// (MoeFfnFp8BlockArgs): the arguments of moe_ffn_fp8_a8 with 3-D scales, w13s
+// [E, 2 ceil(I / 128), ceil(H / 128)] (gate blocks, then up blocks) and w2s
+// [E, ceil(H / 128), ceil(I / 128)]. scratch: at least
+// moe_fp8_block_scratch_bytes. tile: 0 is what serves (moe_fp8_block_tile),
+// 16 and 64 force a kernel family, for measurement and tests; the two
+// families sum the groups of K in different orders. act_out: [T k, I] bf16,
+// receives act by pair in place of the scratch's own array.
+torch::Tensor moe_ffn_fp8_block(torch::Tensor x, torch::Tensor w13q,
+                                torch::Tensor w13s, torch::Tensor w2q,
+                                torch::Tensor w2s, torch::Tensor ids,
+                                torch::Tensor w,
+                                c10::optional<torch::Tensor> scratch,
+                                int64_t tile,
+                                c10::optional<torch::Tensor> act_out) {
+  MoeFfnFp8BlockArgs a{};
+  a.T = check_moe_x(x);
+  a.H = (int)x.size(1);
+  TORCH_CHECK(a.H % 64 == 0, "x.size(1) must be a multiple of 64, got ", a.H);
+  check_tensor(w13q, "w13q", x, "x", at::kFloat8_e4m3fn, {ANY, ANY, a.H});
+  a.E = check_int(w13q.size(0), 1, MOE_MAX_EXPERTS, "w13q.size(0)");
+  TORCH_CHECK(w13q.size(1) % 128 == 0 && w13q.size(1) >= 128, "w13q.size(1) "
+              "= 2 I must be a positive multiple of 128, got ", w13q.size(1));
+  a.I = check_int(w13q.size(1) / 2, 64, INT_MAX, "w13q.size(1) / 2");
+  const int64_t GH = linear_fp8_block_groups(a.H);
+  const int64_t GI = linear_fp8_block_groups(a.I);
+  check_tensor(w13s, "w13s", x, "x", at::kFloat, {a.E, 2 * GI, GH});
+  check_tensor(w2q, "w2q", x, "x", at::kFloat8_e4m3fn, {a.E, a.H, a.I});
+  check_tensor(w2s, "w2s", x, "x", at::kFloat, {a.E, GH, GI});
+  check_tensor(ids, "ids", x, "x", at::kInt, {a.T, ANY});
+  a.k = check_int(ids.size(1), 1, std::min<int64_t>(MOE_MAX_TOPK, a.E),
+                  "ids.size(1)");
+  check_tensor(w, "w", x, "x", at::kFloat, {a.T, a.k});
+  check_aligned16(w13q, "w13q");
+  check_aligned16(w2q, "w2q");
+  check_int((int64_t)a.E * 2 * a.I, 1, INT_MAX, "rows of w13q");
+  check_int((int64_t)a.E * a.H, 1, INT_MAX, "rows of w2q");
+  TORCH_CHECK(tile == 0 || tile == 16 || tile == 64, "tile must be 0, 16 or "
+              "64, got ", tile);
+  const int64_t P = (int64_t)a.T * a.k;
+  check_int(P, 0, INT_MAX - 4, "T k");
+  a.tile = tile ? (int)tile : moe_fp8_block_tile(P, a.E);
+  check_int(moe_tile_bound(P, a.E, a.tile / 16), 0, GRID_YZ_MAX,
+            "work-list tiles");
+  if (act_out.has_value()) {
+    check_tensor(*act_out, "act_out", x, "x", at::kBFloat16, {P, a.I});
+    check_aligned16(*act_out, "act_out");
+  }
+  const MoeBlockScratch s =
+      moe_fp8_block_scratch_layout(a.T, a.k, a.E, a.H, a.I);
+  if (scratch.has_value()) {
+    check_tensor(*scratch, "scratch", x, "x", at::kByte, {ANY});
+    TORCH_CHECK(scratch->size(0) >= s.total, "scratch must hold ", s.total,
+                " bytes, got ", scratch->size(0));
+    check_aligned16(*scratch, "scratch");
+  }
+  auto y = torch::empty({a.T, a.H}, x.options());
+  if (a.T == 0) return y;
+  torch::Tensor buf = scratch.has_value()
+      ? *scratch : torch::empty({s.total}, x.options().dtype(torch::kByte));
+  uint8_t* base = buf.data_ptr<uint8_t>();
+  a.xq = base + s.xq;
+  a.sx = (float*)(base + s.sx);
+  a.act = act_out.has_value() ? act_out->data_ptr() : base + s.act;
+  a.aq = base + s.aq;
+  a.sa = (float*)(base + s.sa);
+  a.y2 = (float*)(base + s.y2);
+  a.tiles = (int32_t*)(base + s.tiles);
+  a.n_tiles = (int32_t*)(base + s.n_tiles);
+  a.perm = (int32_t*)(base + s.perm);
+  a.x = x.data_ptr();
+  a.w13q = w13q.data_ptr();
+  a.w13s = w13s.data_ptr<float>();
+  a.w2q = w2q.data_ptr();
+  a.w2s = w2s.data_ptr<float>();
+  a.ids = ids.data_ptr<int32_t>();
+  a.w = w.data_ptr<float>();
+  a.y = y.data_ptr();
+  CHECK_HIP(lds_moe_ffn_fp8_block(a, cur_stream()));
+  return y;
+}
+
 // ---- sampler ----
 
 // One per-row parameter vector of sample(): [B], on the logits' device.
@@ -1542,6 +1664,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MFMA: the arguments of moe_ffn_fp8, H and I multiples of 64 -> y "
         "[T, H] bf16; tile: measurement knob, never changes y; act_out: "
         "[T k, I] bf16, receives the activation by pair",
+        py::arg("x"), py::arg("w13q"), py::arg("w13s"), py::arg("w2q"),
+        py::arg("w2s"), py::arg("ids"), py::arg("w"),
+        py::arg("scratch") = py::none(), py::arg("tile") = 0,
+        py::arg("act_out") = py::none());
+  m.def("moe_fp8_block_scratch_bytes", &moe_fp8_block_scratch_bytes,
+        "bytes of scratch moe_ffn_fp8_block needs",
+        py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));
+  m.def("moe_ffn_fp8_block", &moe_ffn_fp8_block,
+        "routed expert FFN on block-scaled fp8 experts with group-scaled fp8 "
+        "activations: the arguments of moe_ffn_fp8_a8 with w13s [E, 2 ceil(I "
+        "/ 128), ceil(H / 128)] and w2s [E, ceil(H / 128), ceil(I / 128)] "
+        "fp32 -> y [T, H] bf16; tile: 0 as served, 16 or 64 forces a kernel "
+        "family; act_out: [T k, I] bf16, receives the activation by pair",
         py::arg("x"), py::arg("w13q"), py::arg("w13s"), py::arg("w2q"),
         py::arg("w2s"), py::arg("ids"), py::arg("w"),
         py::arg("scratch") = py::none(), py::arg("tile") = 0,

@@ -427,14 +427,19 @@ class EngineWorker:
         (DEVELOPMENT.md "Mixture of experts"); the router stays in the
         runner's dtype. Both ranks of a P/D pair must use the same value.
 
-        expert_dtype "bf16", "fp8" or "mxfp4" (MoE models only) gives the
-        experts that format whatever weight_dtype says, and weight_dtype
-        then governs wqkv and wo alone: "fp8" with weight_dtype "fp8" is the
-        all-fp8 MoE model, "mxfp4" with weight_dtype "auto" MXFP4 experts
-        under bf16 attention. "auto" is the rule above, under which
-        weight_dtype "fp8" or "fp8_block" alone on an MoE model is an
-        error, and "fp8_block" is no expert_dtype: block-scaled experts are
-        not built.
+        expert_dtype "bf16", "fp8", "fp8_block128" or "mxfp4" (MoE models
+        only) gives the experts that format whatever weight_dtype says, and
+        weight_dtype then governs wqkv and wo alone: "fp8" with weight_dtype
+        "fp8" is the all-fp8 MoE model, "mxfp4" with weight_dtype "auto"
+        MXFP4 experts under bf16 attention. "fp8_block128" stores every
+        expert as e4m3 with one fp32 scale per 128 x 128 block, gate_proj
+        and up_proj blocked apart, and multiplies it with group-scaled e4m3
+        activations at every batch size (DEVELOPMENT.md "Mixture of
+        experts"); with weight_dtype "fp8_block" it is the recipe of the
+        public block-scaled fp8 MoE checkpoints. "auto" is the rule above,
+        under which weight_dtype "fp8" or "fp8_block" alone on an MoE model
+        is an error; the block-scaled expert_dtype is spelled
+        "fp8_block128", and "fp8_block" is no expert_dtype.
 
         activation_dtype "fp8" (with weight_dtype "fp8" only; anything else
         is a ValueError) runs batches above the weight-only kernel's
@@ -451,7 +456,9 @@ class EngineWorker:
         else is a ValueError) runs the experts of batches above the skinny
         kernels' crossover with fp8 activations on the fp8 MFMA
         (DEVELOPMENT.md "Mixture of experts"), under the same caveat. "auto"
-        and "bf16" keep bf16 activations in the experts.
+        and "bf16" keep bf16 activations in the experts. expert_dtype
+        "fp8_block128" implies fp8 activations in the experts: "auto" and
+        "fp8" change nothing there, and "bf16" is a ValueError.
 
         kv_scales selects the per-head scales of an fp8 KV cache
         (KVPool): "none" (unscaled direct cast), "calibrate" (run
@@ -470,7 +477,8 @@ class EngineWorker:
         if config.num_experts and max_loras > 0:
             raise ValueError("LoRA adapters are not supported for an MoE "
                              "model (max_loras must be 0)")
-        if expert_dtype not in ("auto", "bf16", "fp8", "mxfp4"):
+        if expert_dtype not in ("auto", "bf16", "fp8", "fp8_block128",
+                                "mxfp4"):
             raise ValueError(f"unknown expert_dtype {expert_dtype!r}")
         if activation_dtype not in ("auto", "bf16", "fp8"):
             raise ValueError(f"unknown activation_dtype {activation_dtype!r}")
@@ -482,9 +490,11 @@ class EngineWorker:
         if expert_activation_dtype not in ("auto", "bf16", "fp8"):
             raise ValueError("unknown expert_activation_dtype "
                              f"{expert_activation_dtype!r}")
-        if expert_activation_dtype == "fp8" and expert_dtype != "fp8":
+        if expert_activation_dtype == "fp8" and \
+                expert_dtype not in ("fp8", "fp8_block128"):
             raise ValueError('expert_activation_dtype "fp8" needs '
-                             f'expert_dtype "fp8", got {expert_dtype!r}')
+                             'expert_dtype "fp8" (or "fp8_block128", which '
+                             f'implies it), got {expert_dtype!r}')
         if expert_dtype != "auto" and not config.num_experts:
             raise ValueError(f"expert_dtype {expert_dtype!r} needs an MoE "
                              "model: a dense model has no experts")

@@ -173,8 +173,9 @@ class LlamaRunner:
         # bf16 scratch below is never allocated
         self.activation_dtype = "bf16"
         self._fp8_scratch: Dict[int, torch.Tensor] = {}
-        # ops.moe_ffn / moe_ffn_mxfp4 / moe_ffn_fp8 / moe_ffn_fp8_a8 scratch,
-        # one per stream, sized by the largest T seen
+        # ops.moe_ffn / moe_ffn_mxfp4 / moe_ffn_fp8 / moe_ffn_fp8_a8 /
+        # moe_ffn_fp8_block scratch, one per stream, sized by the largest T
+        # seen
         self._moe_scratch: Dict[int, torch.Tensor] = {}
         # "fp8" (set_expert_activation_dtype): fp8 experts at batches of
         # more than _moe_a8_min_rows mean rows per expert (T k / E) go
@@ -184,6 +185,8 @@ class LlamaRunner:
         # (profiles/moe_fp8_a8.md)
         self.expert_activation_dtype = "bf16"
         self._moe_a8_min_rows = 8
+        # "fp8_block128" experts (a 3-D fp32 scale) go through
+        # ops.moe_ffn_fp8_block at every batch size
 
     def weight_bytes(self) -> int:
         tensors = [self.embed, self.lm_head, self.final_norm]
@@ -222,8 +225,9 @@ class LlamaRunner:
         if experts and weight_dtype == "fp8_block":
             raise ValueError(
                 'weight_dtype "fp8_block" alone is not supported for an MoE '
-                "model: block-scaled experts are not built; pass expert_dtype "
-                '"bf16", "fp8" or "mxfp4" and fp8_block covers wqkv and wo')
+                'model: pass expert_dtype "fp8_block128" for block-scaled '
+                'experts (or "bf16", "fp8" or "mxfp4") and fp8_block covers '
+                "wqkv and wo")
         if experts and weight_dtype != "mxfp4":
             raise ValueError(
                 f"weight_dtype {weight_dtype!r} alone is not supported for an "
@@ -290,10 +294,20 @@ class LlamaRunner:
         hidden_size and moe_intermediate_size multiples of 64. Smaller
         batches keep ops.moe_ffn_fp8, so the quantisation a row sees depends
         on the size of the batch it ran in. "auto" and "bf16" change
-        nothing."""
+        nothing. "fp8_block128" experts are a W8A8 format by definition:
+        "auto" and "fp8" change nothing there, and "bf16" is a ValueError."""
         if expert_activation_dtype not in ("auto", "bf16", "fp8"):
             raise ValueError("unknown expert_activation_dtype "
                              f"{expert_activation_dtype!r}")
+        if self.expert_dtype == "fp8_block128":
+            if expert_activation_dtype == "bf16":
+                raise ValueError(
+                    'expert_activation_dtype "bf16" is not available with '
+                    'expert_dtype "fp8_block128": the format is defined '
+                    "with fp8 activations, one scale per row and 128-wide "
+                    "group, and no kernel multiplies its experts by bf16 "
+                    "rows")
+            return
         if expert_activation_dtype != "fp8":
             return
         if self.expert_dtype != "fp8":
@@ -313,7 +327,7 @@ class LlamaRunner:
         whose experts are still bf16 (or, from quantize_weights on a runner
         it has converted before, already `allowed`)."""
         c = self.cfg
-        if expert_dtype not in ("fp8", "mxfp4"):
+        if expert_dtype not in ("fp8", "fp8_block128", "mxfp4"):
             raise ValueError(f"unknown expert_dtype {expert_dtype!r}")
         if not c.num_experts:
             raise ValueError("expert_dtype needs an MoE model: a dense model "
@@ -330,6 +344,12 @@ class LlamaRunner:
                 "mxfp4 experts need hidden_size and moe_intermediate_size to "
                 f"be multiples of 32, got {c.hidden_size} and "
                 f"{c.moe_intermediate_size}")
+        if expert_dtype == "fp8_block128" and (c.hidden_size % 64 or
+                                               c.moe_intermediate_size % 64):
+            raise ValueError(
+                "fp8_block128 experts need hidden_size and "
+                "moe_intermediate_size to be multiples of 64, got "
+                f"{c.hidden_size} and {c.moe_intermediate_size}")
 
     def quantize_experts(self, expert_dtype: str) -> None:
         """Convert w13 and w2 of every layer in place, expert by expert, each
@@ -339,21 +359,32 @@ class LlamaRunner:
         config. "mxfp4": (w13q [E, 2 I, H / 2], w13s [E, 2 I, H / 32]) and
         (w2q [E, H, I / 2], w2s [E, H, I / 32]), all uint8;
         hidden_size and moe_intermediate_size must be multiples of 32, the
-        MX group. wqkv, wo, the router, the embedding, lm_head and the norms
+        MX group. "fp8_block128" (DEVELOPMENT.md "Mixture of experts"): the
+        block-scaled pairs of ops.ref.quantize_experts_fp8_block, (w13q
+        [E, 2 I, H], w13s [E, 2 ceil(I / 128), ceil(H / 128)] fp32) with the
+        gate and the up rows blocked apart, and (w2q [E, H, I], w2s
+        [E, ceil(H / 128), ceil(I / 128)]), told apart from "fp8" by their
+        3-D scale and multiplied with fp8 activations at every batch size;
+        hidden_size and moe_intermediate_size must be multiples of 64. wqkv,
+        wo, the router, the embedding, lm_head and the norms
         are left alone. Experts that are already quantised cannot be
         converted again: the bf16 weights are gone."""
         self._check_expert_dtype(expert_dtype, "bf16")
-        quantize = ops_ref.quantize_experts_fp8 if expert_dtype == "fp8" \
-            else ops_ref.quantize_experts_mxfp4
+        quantize = {
+            "fp8": lambda W, halves: ops_ref.quantize_experts_fp8(W),
+            "fp8_block128": ops_ref.quantize_experts_fp8_block,
+            "mxfp4": lambda W, halves: ops_ref.quantize_experts_mxfp4(W),
+        }[expert_dtype]
         for layer in self.layers:
-            for name in ("w13", "w2"):
-                layer[name] = quantize(layer[name])
+            for name, halves in (("w13", 2), ("w2", 1)):
+                layer[name] = quantize(layer[name], halves)
         self.expert_dtype = expert_dtype
 
     def dense_layers(self) -> List[Dict[str, torch.Tensor]]:
         """self.layers with the four projections as fp32 [in, out] tensors,
         an fp8, fp8_block or mxfp4 pair dequantised exactly: the weights the
-        forward pass applies. MXFP4 and fp8 experts come back as fp32 [E, out, in]."""
+        forward pass applies. MXFP4, fp8 and block-scaled fp8 experts come
+        back as fp32 [E, out, in]."""
         def dense(w):
             if not isinstance(w, tuple):
                 return w.float()
@@ -363,14 +394,17 @@ class LlamaRunner:
                 return (w[0].float() * ops_ref.expand_fp8_block_scale(
                     w[1], *w[0].shape)).t()
             return (w[0].float() * w[1][:, None]).t()
-        def experts(w):
+        def experts(w, halves):
             if not isinstance(w, tuple):
                 return w
+            if w[1].dim() == 3 and w[1].dtype == torch.float32:
+                return ops_ref.dequant_experts_fp8_block(*w, halves=halves)
             return ops_ref.dequant_experts_mxfp4(*w) \
                 if w[0].dtype == torch.uint8 else \
                 ops_ref.dequant_experts_fp8(*w)
         return [{k: dense(w) if k in LORA_TARGETS else
-                 experts(w) if k in ("w13", "w2") else w
+                 experts(w, 2 if k == "w13" else 1) if k in ("w13", "w2")
+                 else w
                  for k, w in layer.items()} for layer in self.layers]
 
     # ---- mixture of experts (DEVELOPMENT.md "Mixture of experts") ----
@@ -411,17 +445,21 @@ class LlamaRunner:
         c = self.cfg
         ids, w = ops.moe_route(x, layer["router"], c.experts_per_token,
                                c.norm_topk_prob)
-        # a bf16 tensor, an MXFP4 pair (uint8) or an fp8 pair
-        mx = a8 = False
+        # a bf16 tensor, an MXFP4 pair (uint8), an fp8 pair or a block-scaled
+        # fp8 pair (a 3-D fp32 scale)
+        mx = a8 = blk = False
         if not isinstance(layer["w13"], tuple):
             ffn, experts = ops.moe_ffn, (layer["w13"], layer["w2"])
         else:
             mx = layer["w13"][0].dtype == torch.uint8
             # host arithmetic on the batch size alone: no sync
-            a8 = not mx and self.expert_activation_dtype == "fp8" and \
+            blk = not mx and layer["w13"][1].dim() == 3
+            a8 = not mx and not blk and \
+                self.expert_activation_dtype == "fp8" and \
                 x.shape[0] * c.experts_per_token > \
                 self._moe_a8_min_rows * c.num_experts
             ffn = ops.moe_ffn_mxfp4 if mx else \
+                ops.moe_ffn_fp8_block if blk else \
                 ops.moe_ffn_fp8_a8 if a8 else ops.moe_ffn_fp8
             experts = (*layer["w13"], *layer["w2"])
         if not x.is_cuda:
@@ -429,8 +467,9 @@ class LlamaRunner:
         key = torch.cuda.current_stream(x.device).cuda_stream
         shape = (x.shape[0], c.experts_per_token, c.num_experts,
                  c.hidden_size, c.moe_intermediate_size)
-        need = ops.moe_scratch_bytes(*shape, mxfp4=mx)
-        if self.expert_activation_dtype == "fp8":
+        need = ops.moe_fp8_block_scratch_bytes(*shape) if blk else \
+            ops.moe_scratch_bytes(*shape, mxfp4=mx)
+        if not blk and self.expert_activation_dtype == "fp8":
             # one buffer serves both ops: the larger of the two needs
             need = max(need, ops.moe_fp8_a8_scratch_bytes(*shape))
         buf = self._moe_scratch.get(key)

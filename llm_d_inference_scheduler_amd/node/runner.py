@@ -92,9 +92,11 @@ class NodeConfig:
     # values along K, which on an MoE model covers the experts and is the
     # only quantised choice); the same on every rank that exchanges KV
     weight_dtype: str = "auto"
-    # auto|bf16|fp8|mxfp4, MoE models only: the format of the experts, with
-    # weight_dtype then governing wqkv and wo alone (fp8 = e4m3 experts, a
-    # scale per expert and output channel); auto = the rule above
+    # auto|bf16|fp8|fp8_block128|mxfp4, MoE models only: the format of the
+    # experts, with weight_dtype then governing wqkv and wo alone (fp8 = e4m3
+    # experts, a scale per expert and output channel; fp8_block128 = e4m3
+    # experts, a scale per expert and 128 x 128 block, with e4m3 activations
+    # scaled per row and 128-wide group); auto = the rule above
     expert_dtype: str = "auto"
     # auto|bf16|fp8 (fp8 = per-token dynamic e4m3 activations on the fp8 MFMA
     # for batches above the weight-only kernel's crossover; needs

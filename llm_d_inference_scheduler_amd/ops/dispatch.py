@@ -410,6 +410,34 @@ def moe_ffn_fp8_a8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
                               act_out=act_out)
 
 
+def moe_fp8_block_scratch_bytes(T: int, k: int, E: int, H: int,
+                                I: int) -> int:
+    """Bytes of the scratch ops.moe_ffn_fp8_block takes for T tokens."""
+    return hip_ops().moe_fp8_block_scratch_bytes(T, k, E, H, I)
+
+
+def moe_ffn_fp8_block(x: torch.Tensor, w13q: torch.Tensor,
+                      w13s: torch.Tensor, w2q: torch.Tensor,
+                      w2s: torch.Tensor, ids: torch.Tensor, w: torch.Tensor,
+                      scratch: Optional[torch.Tensor] = None,
+                      act_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_ffn on block-scaled fp8 experts (DEVELOPMENT.md "Mixture of
+    experts"), the pairs of ops.ref.quantize_experts_fp8_block: w13q
+    [E, 2 I, H] with w13s [E, 2 ceil(I / 128), ceil(H / 128)] (halves=2: gate
+    blocks, then up blocks) and w2q [E, H, I] with w2s [E, ceil(H / 128),
+    ceil(I / 128)]. x and the activation are quantised per row and 128-wide
+    group by quantize_groups_fp8 and both expert GEMMs run on the fp8 MFMA,
+    every group's sum scaled into the fp32 accumulator. H % 64 == 0 and
+    I % 64 == 0. scratch (GPU only): at least moe_fp8_block_scratch_bytes.
+    act_out: a [T k, I] bf16 tensor that receives bf16(silu(g) * u) of pair
+    t k + j."""
+    if _use_hip(x):
+        return _ext.moe_ffn_fp8_block(x, w13q, w13s, w2q, w2s, ids, w,
+                                      scratch, 0, act_out)
+    return ref.moe_ffn_fp8_block(x, w13q, w13s, w2q, w2s, ids, w,
+                                 act_out=act_out)
+
+
 def move_blocks(pool: torch.Tensor, staging: torch.Tensor,
                 block_ids: torch.Tensor, is_scatter: bool) -> None:
     if _use_hip(pool):

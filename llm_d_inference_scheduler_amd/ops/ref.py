@@ -1016,6 +1016,90 @@ def moe_ffn_fp8_a8(x: torch.Tensor, w13q: torch.Tensor, w13s: torch.Tensor,
     return y.to(x.dtype)
 
 
+def quantize_experts_fp8_block(W: torch.Tensor, halves: int = 1):
+    """W [E, out, in] -> (wq [E, out, in] float8_e4m3fn, scale [E, halves *
+    ceil((out / halves) / 128), ceil(in / 128)] fp32), expert by expert: each
+    of the `halves` row ranges is a matrix of its own to
+    quantize_weight_fp8_block, with a grid of 128-row blocks that starts at
+    its first row. w13 takes halves=2, the gate rows [0, I) and the up rows
+    [I, 2 I) as the checkpoints store gate_proj and up_proj (with I % 128 !=
+    0 this is not the blocking of the merged [2 I, H] matrix); w2 takes 1."""
+    rows = W.shape[1] // halves
+    wq, scale = [], []
+    for e in range(W.shape[0]):
+        pairs = [quantize_weight_fp8_block(W[e, h * rows:(h + 1) * rows].t())
+                 for h in range(halves)]
+        wq.append(torch.cat([p[0] for p in pairs]))
+        scale.append(torch.cat([p[1] for p in pairs]))
+    return torch.stack(wq), torch.stack(scale)
+
+
+def _expand_experts_fp8_block(scale: torch.Tensor, n_out: int, n_in: int,
+                              halves: int) -> torch.Tensor:
+    """scale [E, halves * NBk, G] -> [E, out, in]: every element's scale."""
+    E, rows = scale.shape[0], n_out // halves
+    nb = scale.shape[1] // halves
+    s = scale.reshape(E * halves, nb, -1).repeat_interleave(FP8_BLOCK, 1)
+    s = s[:, :rows].repeat_interleave(FP8_BLOCK, 2)[:, :, :n_in]
+    return s.reshape(E, n_out, n_in)
+
+
+def dequant_experts_fp8_block(wq: torch.Tensor, scale: torch.Tensor,
+                              halves: int = 1,
+                              dtype=torch.float32) -> torch.Tensor:
+    """[E, out, in] in `dtype`: float(wq) * its block's scale in fp32."""
+    return (wq.float() * _expand_experts_fp8_block(
+        scale, wq.shape[1], wq.shape[2], halves)).to(dtype)
+
+
+def _grouped_fp8_block(xq: torch.Tensor, sx: torch.Tensor, wq: torch.Tensor,
+                       col: torch.Tensor) -> torch.Tensor:
+    """sum_g sx[m, g] * col[n, g] * sum_{k in g} xq[m, k] wq[n, k] as
+    linear_fp8_block sums it: fp32, groups in order."""
+    xf, wf = xq.float(), wq.float()
+    y = torch.zeros(xf.shape[0], wf.shape[0], device=xq.device)
+    for g in range(sx.shape[1]):
+        k = slice(g * FP8_BLOCK, min((g + 1) * FP8_BLOCK, wf.shape[1]))
+        y += (xf[:, k] @ wf[:, k].t()) * (sx[:, g, None] * col[None, :, g])
+    return y
+
+
+def moe_ffn_fp8_block(x: torch.Tensor, w13q: torch.Tensor,
+                      w13s: torch.Tensor, w2q: torch.Tensor,
+                      w2s: torch.Tensor, ids: torch.Tensor, w: torch.Tensor,
+                      act_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_ffn_fp8_a8 on block-scaled experts (quantize_experts_fp8_block,
+    w13 with halves=2): both activations quantised by quantize_groups_fp8,
+    both GEMMs summed as linear_fp8_block sums them. act = bf16(silu(g) * u)
+    is quantised per (token, slot) pair and 128-wide group of I; act_out
+    [T k, I], if given, receives it at row t k + j."""
+    T, H = x.shape
+    I, k = w13q.shape[1] // 2, ids.shape[1]
+    xq, sx = quantize_groups_fp8(x)
+    # every output row's scales over the groups of K: [E, out, G]
+    rows = lambda s, n, halves: s.reshape(
+        s.shape[0] * halves, -1, s.shape[2]).repeat_interleave(
+            FP8_BLOCK, 1)[:, :n // halves].reshape(s.shape[0], n, -1)
+    col13, col2 = rows(w13s, 2 * I, 2), rows(w2s, H, 1)
+    y2 = torch.zeros(T, k, H, dtype=torch.float32, device=x.device)
+    for e in range(w13q.shape[0]):
+        t, j = (ids == e).nonzero(as_tuple=True)
+        if t.numel() == 0:
+            continue
+        g, u = _grouped_fp8_block(xq[t], sx[t], w13q[e], col13[e]).split(
+            I, dim=-1)
+        act = (g * torch.sigmoid(g) * u).to(x.dtype)
+        if act_out is not None:
+            act_out[t * k + j] = act.to(act_out.dtype)
+        aq, sa = quantize_groups_fp8(act)
+        y2[t, j] = _grouped_fp8_block(aq, sa, w2q[e], col2[e]) * \
+            w[t, j].float()[:, None]
+    y = y2[:, 0]
+    for j in range(1, k):
+        y = y + y2[:, j]
+    return y.to(x.dtype)
+
+
 _PREFIX_MODEL = PrefixModel()
 hash_prompts = _PREFIX_MODEL.hash_prompts
 table_update = _PREFIX_MODEL.table_update

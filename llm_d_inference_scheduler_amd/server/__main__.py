@@ -49,11 +49,16 @@ def parse_args(argv=None):
                         "an MoE model takes mxfp4 only, experts included, "
                         "unless --expert-dtype is given")
     p.add_argument("--expert-dtype", default="auto",
-                   choices=["auto", "bf16", "fp8", "mxfp4"],
+                   choices=["auto", "bf16", "fp8", "fp8_block128", "mxfp4"],
                    help="MoE models: the format of the experts, with "
                         "--weight-dtype then governing wqkv and wo alone "
                         "(fp8: e4m3 with one scale per expert and output "
-                        "channel; mxfp4 as above); auto: the experts follow "
+                        "channel; fp8_block128: e4m3 with one scale per "
+                        "expert and 128 x 128 block, run with e4m3 "
+                        "activations scaled per row and 128-wide group, "
+                        "with --weight-dtype fp8_block the recipe of the "
+                        "public block-scaled fp8 MoE checkpoints; mxfp4 as "
+                        "above); auto: the experts follow "
                         "--weight-dtype")
     p.add_argument("--activation-dtype", default="auto",
                    choices=["auto", "bf16", "fp8"],
@@ -66,7 +71,9 @@ def parse_args(argv=None):
                         "of its batch")
     p.add_argument("--expert-activation-dtype", default="auto",
                    choices=["auto", "bf16", "fp8"],
-                   help="MoE models, fp8 (needs --expert-dtype fp8): the "
+                   help="MoE models, fp8 (needs --expert-dtype fp8; "
+                        "fp8_block128 experts always run fp8 activations "
+                        "and reject bf16 here): the "
                         "experts of prefill-sized batches run with per-row "
                         "dynamic e4m3 activations on the fp8 MFMA")
     p.add_argument("--kv-scales", default=None,

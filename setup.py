@@ -46,6 +46,7 @@ hip_ops = cpp_extension.CUDAExtension(
         "csrc/hip/linear_mxfp4.hip",
         "csrc/hip/moe.hip",
         "csrc/hip/moe_fp8_a8.hip",
+        "csrc/hip/moe_fp8_block.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],

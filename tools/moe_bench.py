@@ -2,7 +2,7 @@
 Qwen3-30B-A3B shapes (results: profiles/moe.md).
 
     python tools/moe_bench.py [--rounds 7] [--copies 8]
-                              [--weights mxfp4|fp8|fp8_a8]
+                              [--weights mxfp4|fp8|fp8_a8|fp8_block128]
 
 One layer: H 2048, 128 experts of I 768, 8 a token, for T in {1, 16, 64, 256,
 1024, 4096}. Arms, timed in one process in interleaved rounds (arm order
@@ -56,6 +56,20 @@ _moe_a8_min_rows, and `ratio` fp8 over fp8_a8. At T = 64 the fp8_a8 output is
 judged by the two-stage float64 bound of tests/moe_fp8_a8_cases.py; at every
 larger T its first 64 rows must be those bits again (a row's bits do not
 depend on the batch).
+
+--weights fp8_block128 (results: profiles/moe_fp8_block.md) times
+ops.moe_ffn_fp8_block on block-scaled experts for T in {1, 16, ..., 4096}:
+  block     as served (moe_fp8_block_tile)
+  block16   the 16-row registers-only kernels forced
+  block64   the 64-row LDS tiles forced
+  fp8_a8, fp8   ops.moe_ffn_fp8_a8 and ops.moe_ffn_fp8 on per-channel pairs of
+            the same experts, for context
+  quant_x, quant_act   ops.quantize_groups_fp8 on [T, H] and on [T k, I]: the
+            two quantiser passes on their own
+Every arm but the last two includes ops.moe_route. `floor` is 1 byte a weight
+plus the block scales of the touched experts, the router, and x in and y out.
+Up to T = 64 both forced arms are judged by the two-stage float64 bound of
+tests/moe_fp8_block_cases.py before they are timed.
 """
 import argparse
 import json
@@ -71,6 +85,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import moe_cases  # noqa: E402
 import moe_fp8_a8_cases  # noqa: E402
+import moe_fp8_block_cases  # noqa: E402
 from llm_d_inference_scheduler_amd import ops  # noqa: E402
 from llm_d_inference_scheduler_amd.models.configs import (  # noqa: E402
     QWEN3_30B_A3B)
@@ -146,8 +161,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--copies", type=int, default=8)
-    ap.add_argument("--weights", choices=["bf16", "mxfp4", "fp8", "fp8_a8"],
-                    default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "mxfp4", "fp8", "fp8_a8",
+                                          "fp8_block128"], default="bf16")
     args = ap.parse_args()
     ops.hip_ops()
     c = QWEN3_30B_A3B
@@ -162,6 +177,8 @@ def main():
     expert_bytes = 3 * I * H * 2
     if args.weights == "fp8_a8":
         return main_fp8_a8(args, routers, w13s, w2s, randn)
+    if args.weights == "fp8_block128":
+        return main_fp8_block(args, routers, w13s, w2s, randn)
     if args.weights != "bf16":
         return main_quantised(args, routers, w13s, w2s, randn)
     for T in TS:
@@ -308,6 +325,88 @@ def main_fp8_a8(args, routers, w13s, w2s, randn):
             T=T, H=H, I=I, E=E, k=k, copies=n, rows=T * k / E, **res,
             ratio=round(res["fp8"] / res["fp8_a8"], 2))), flush=True)
         del xs, scratch
+
+
+def main_fp8_block(args, routers, w13s, w2s, randn):
+    """--weights fp8_block128: ops.moe_ffn_fp8_block as served and with each
+    kernel family forced, with ops.moe_ffn_fp8 and ops.moe_ffn_fp8_a8 on
+    per-channel pairs of the same experts for context."""
+    n, (E, _, H), I = args.copies, w13s[0].shape, w2s[0].shape[2]
+    k = QWEN3_30B_A3B.experts_per_token
+    ref, ext = ops.ref, ops.hip_ops()
+    b13s, b2s, q13s, q2s = [], [], [], []
+    for i in range(n):
+        b13s.append(ref.quantize_experts_fp8_block(w13s[i], halves=2))
+        b2s.append(ref.quantize_experts_fp8_block(w2s[i]))
+        q13s.append(ref.quantize_experts_fp8(w13s[i]))
+        q2s.append(ref.quantize_experts_fp8(w2s[i]))
+        w13s[i] = w2s[i] = None
+    scale_bytes = (b13s[0][1][0].numel() + b2s[0][1][0].numel()) * 4
+    for T in TS:
+        xs = [randn(T, H).bfloat16() for _ in range(n)]
+        acts = [randn(T * k, I).bfloat16() for _ in range(n)]
+        scratch = {
+            "block": ops.moe_fp8_block_scratch_bytes(T, k, E, H, I),
+            "fp8_a8": ops.moe_fp8_a8_scratch_bytes(T, k, E, H, I),
+            "fp8": ops.moe_scratch_bytes(T, k, E, H, I)}
+        scratch = {a: torch.empty(b, dtype=torch.uint8, device=DEV)
+                   for a, b in scratch.items()}
+
+        def block(tile):
+            def call(i, act_out=None):
+                ids, w = ops.moe_route(xs[i], routers[i], k, True)
+                return ext.moe_ffn_fp8_block(xs[i], *b13s[i], *b2s[i], ids, w,
+                                             scratch["block"], tile, act_out)
+            return call
+
+        def a8(i):
+            ids, w = ops.moe_route(xs[i], routers[i], k, True)
+            return ops.moe_ffn_fp8_a8(xs[i], *q13s[i], *q2s[i], ids, w,
+                                      scratch["fp8_a8"])
+
+        def fp8(i):
+            ids, w = ops.moe_route(xs[i], routers[i], k, True)
+            return ops.moe_ffn_fp8(xs[i], *q13s[i], *q2s[i], ids, w,
+                                   scratch["fp8"])
+
+        if T <= 64:     # judged on the CPU: small batches only
+            ids, w = ops.moe_route(xs[0], routers[0], k, True)
+            cpu = [t.cpu() for t in (xs[0], *b13s[0], *b2s[0], ids, w)]
+            dense = (ref.dequant_experts_fp8_block(cpu[1], cpu[2], halves=2,
+                                                   dtype=torch.float64),
+                     ref.dequant_experts_fp8_block(cpu[3], cpu[4],
+                                                   dtype=torch.float64))
+            for tile in (16, 64):
+                act = torch.empty(T * k, I, dtype=torch.bfloat16, device=DEV)
+                y = block(tile)(0, act)
+                e1, e2 = moe_fp8_block_cases.excess(y.cpu(), act.cpu(), cpu,
+                                                    dense)
+                if e1 > 0 or e2 > 0:
+                    raise SystemExit(
+                        f"T={T} tile {tile}: excess {e1:.3e} {e2:.3e}")
+                print(f"# T={T} tile {tile} excess {e1:.3e} {e2:.3e}",
+                      flush=True)
+        touched = statistics.mean(
+            int(torch_route(xs[i], routers[i], k)[0].unique().numel())
+            for i in range(n))
+        fns = {"block": rotating(block(0), n),
+               "block16": rotating(block(16), n),
+               "block64": rotating(block(64), n),
+               "fp8_a8": rotating(a8, n), "fp8": rotating(fp8, n),
+               # the two quantiser passes on their own (they allocate their
+               # outputs, which the op does not)
+               "quant_x": rotating(
+                   lambda i: ops.quantize_groups_fp8(xs[i]), n),
+               "quant_act": rotating(
+                   lambda i: ops.quantize_groups_fp8(acts[i]), n)}
+        res = bench(fns, args.rounds)
+        print(json.dumps(dict(
+            T=T, H=H, I=I, E=E, k=k, copies=n, rows=T * k / E,
+            experts=round(touched, 1),
+            floor=round((touched * (3 * I * H + scale_bytes) + E * H * 2 +
+                         T * H * 4) / HBM_BYTES_PER_US, 2),
+            **res)), flush=True)
+        del xs, acts, scratch
 
 
 if __name__ == "__main__":
